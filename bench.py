@@ -8,7 +8,11 @@ independent k=128 blocks per GPU, inputs already resident in HBM.  N GPUs shard
 independent blocks (weak scaling, no collective on the data path); the only
 collectives are the timing barrier and the max-over-ranks of the elapsed time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--k 128] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--k 128] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+result line.  --full adds everything else: the output check against the committed digests, the per-kernel pass and
+rooflines, the HBM ceilings, configs C2 / C4 / C5, the host-buffer and per-axis shapes and the CPU baseline.
 """
 import argparse
 import json
@@ -1146,6 +1150,13 @@ def main():
                          "split: ONE k-square split over all ranks with an RCCL all-to-all (config C5, --k 512)")
     ap.add_argument("--k512-split-helper", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-k512-split", action="store_true", help="skip config C5's split after the timed loop")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the output check against the committed digests, the "
+                         "per-kernel pass with its rooflines and HBM ceilings, config C5's split, the extras and the "
+                         "CPU baseline (the --no-* options take parts of it out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; the EDS as a "
+                         "fixed seeded sample of its cells)")
     args = ap.parse_args()
     if args.k512_split_helper:
         return split_helper_main(args)
@@ -1159,7 +1170,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # config C5 at N > 1: the helper process starts before this process touches the GPU (SplitHelper)
     helper = None
-    if rank == 0 and world > 1 and not args.no_k512_split:
+    if rank == 0 and world > 1 and args.full and not args.no_k512_split:
         helper = SplitHelper(split_devices(world), args.dry_run)
     try:
         return bench_main(args, world, rank, local, helper)
@@ -1247,27 +1258,12 @@ def bench_main(args, world, rank, local, helper):
     blocks = world * B * args.steps
     value = blocks / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, k, B, d_eds, d_roots, d_dah, d_status)
     # the timed steps' output: every block's DAH against the committed digests (tests/golden/bench_digests.json)
-    check = check_dahs(d_dah.cpu().numpy(), k, B, rank, nd)
+    check = check_dahs(d_dah.cpu().numpy(), k, B, rank, nd) if args.full else None
     ranks_rep = rank_report(world, rank, backend, dev, cpu_group, ms_per_step=1000.0 * mine_s / args.steps,
                             blocks=B * args.steps, check=check)
-
-    # per-kernel durations: HIP events on the launch stream, separate pass (profiling adds event records)
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    prof_steps = max(2, min(5, args.steps))
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize(dev)
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
-    kern = {n: {"avg_ms": ms / max(1, cnt), "launches": cnt, "total_ms": ms} for n, (ms, cnt) in prof.items()}
-    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    ceil = hbm_ceilings(dev.index) if rank == 0 else None
-    mix, mix_src = isa_mix()
-    rooflines = {n: kernel_roofline(n, kern[n], k, B, prof_steps, ncu, ceil, mix) for n in kern}
-    dom = max(kern, key=lambda n: kern[n]["total_ms"])
-    roofline = dict(rooflines[dom], kernel=dom)
     path_gbs = block_bytes(k) * value / world / 1e9
     comp_per_s = block_compressions_engine(k) * value / world
 
@@ -1289,16 +1285,55 @@ def bench_main(args, world, rank, local, helper):
                                f"k={k} blocks per GPU per step (configs[1] per block, batched as configs[2])",
                    "k": k, "blocks_per_gpu_per_step": B, "share_size": 512,
                    "parallelism": f"blocks x{world}" + (" (ranks share one device, gloo)" if shared else "")},
+        "ranks": ranks_rep,
+        "path_hbm_gbs": round(path_gbs, 1),
+        "sha256_compressions_per_s": comp_per_s,
+    }
+    if args.full:
+        def release():  # the step's large device buffers: the extras need the memory
+            nonlocal d_eds, d_roots, d_ods
+            del d_eds, d_roots, d_ods
+
+        full_measure(args, result, ctx, dev, world, rank, cpu_group, helper, step, release, value, check)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    ctx.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measure(args, result, ctx, dev, world, rank, cpu_group, helper, step, release, value, check):
+    """--full: everything beside the headline, added to `result` after the timed steps -- the per-kernel pass with
+    its rooflines and the HBM ceilings, config C5's split, the extras (C2, C4, commitments, host buffers, proofs,
+    k=512, square construction, the per-axis seams) and the CPU baseline.  `release` frees the step's device buffers
+    (called before the extras; `step` is not run after it)."""
+    import torch
+    import torch.distributed as dist
+    k, B = args.k, args.batch
+    # per-kernel durations: HIP events on the launch stream, separate pass (profiling adds event records)
+    ctx.profile_reset()
+    ctx.profile_enable(True)
+    prof_steps = max(2, min(5, args.steps))
+    for _ in range(prof_steps):
+        step()
+    torch.cuda.synchronize(dev)
+    prof = ctx.profile_read()
+    ctx.profile_enable(False)
+    kern = {n: {"avg_ms": ms / max(1, cnt), "launches": cnt, "total_ms": ms} for n, (ms, cnt) in prof.items()}
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    ceil = hbm_ceilings(dev.index) if rank == 0 else None
+    mix, mix_src = isa_mix()
+    rooflines = {n: kernel_roofline(n, kern[n], k, B, prof_steps, ncu, ceil, mix) for n in kern}
+    dom = max(kern, key=lambda n: kern[n]["total_ms"])
+    roofline = dict(rooflines[dom], kernel=dom)
+    result.update({
         "roofline": roofline,
         "kernel_rooflines": {n: v for n, v in rooflines.items() if n != dom},
         "hbm_ceilings": ceil,
         "isa_mix_source": mix_src,
         "output_check": check,
-        "ranks": ranks_rep,
-        "path_hbm_gbs": round(path_gbs, 1),
-        "sha256_compressions_per_s": comp_per_s,
         "kernels_ms": {n: round(v["avg_ms"], 4) for n, v in kern.items()},
-    }
+    })
     gpu = {}
     # config C5's product path: one k=512 square over every device the ranks use (G = N; helper process, RCCL) and
     # on one device (G = 1); at N = 1 in this process
@@ -1314,7 +1349,7 @@ def bench_main(args, world, rank, local, helper):
         except Exception as e:  # reported, never the headline's exit code
             result["k512_split"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0 and world == 1 and not args.no_extras:
-        del d_eds, d_roots, d_ods
+        release()
         torch.cuda.empty_cache()
         result["c2_single_block"] = single_block_measure(ctx, dev)
         result["repair_c4"] = repair_measure(ctx)
@@ -1329,18 +1364,54 @@ def bench_main(args, world, rank, local, helper):
         except Exception as e:  # reported, never the headline's exit code
             result["per_axis"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cb = cpu_baseline(k, args.cpu_seconds, gpu)
+        result["cpu_baseline"] = cpu_baseline(k, args.cpu_seconds, gpu)
         result["gpu_vs_cpu"] = gpu_vs_cpu(result, value)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 # BASELINE.json's metric, verbatim (the driver matches the line against it)
 METRIC = "ODS\u2192EDS+DAH blocks/sec at k=128 (1/8 GPU); achieved HBM GB/s"
 DISTINCT_ODS = 16  # distinct synthetic squares per rank (tests/golden/make_bench_digests.py covers ranks 0..7)
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # all .npy files of one --dump-outputs together stay under 64 MB
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(out_dir, rank, world, k, B, d_eds, d_roots, d_dah, d_status):
+    """--dump-outputs: what the last timed step left in the caller's buffers, as float32 / float64 .npy files.
+      dah.npy          (B, 32)      every block's DataAvailabilityHeader hash
+      status.npy       (B,)         the namespace-order status words (-1 = ok), float64
+      roots.npy        (n, 4k, 90)  row roots then column roots (the 90-B nodes, without the records' padding) of
+                                    the blocks in roots_block_index.npy (all B when they fit half the budget)
+      eds_cells.npy    (m, 512)     a fixed, seeded sample of the B * 4k^2 EDS cells (shares), sorted by position;
+      eds_cell_index.npy (m,)       their positions block * 4k^2 + row * 2k + col, float64
+    The sample depends on k and B only, so two runs with the same arguments write the same cells.  Ranks other than 0
+    of a multi-rank run write <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 or rank == 0 else f"_rank{rank}"
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+    w = 2 * k
+    rng = np.random.default_rng(DUMP_SEED)
+    save("dah", d_dah.cpu().numpy().astype(np.float32))
+    save("status", d_status.cpu().numpy().astype(np.float64))
+    budget = DUMP_BUDGET_BYTES - B * 32 * 4 - B * 8
+    per_block = 2 * w * 90 * 4
+    nb = max(1, min(B, budget // 2 // per_block))
+    blocks = np.arange(B) if nb == B else np.sort(rng.choice(B, nb, replace=False))
+    roots = d_roots.view(B, 2 * w, 96)[torch.from_numpy(blocks).to(d_roots.device)][:, :, :90]
+    save("roots", roots.cpu().numpy().astype(np.float32))
+    save("roots_block_index", blocks.astype(np.float64))
+    budget -= nb * per_block + nb * 8
+    ncells = B * w * w
+    m = max(1, min(ncells, budget // (512 * 4 + 8)))
+    cells = np.sort(rng.choice(ncells, m, replace=False))
+    eds = d_eds.view(ncells, 512)[torch.from_numpy(cells).to(d_eds.device)]
+    save("eds_cells", eds.cpu().numpy().astype(np.float32))
+    save("eds_cell_index", cells.astype(np.float64))
 
 
 def check_dahs(dah, k, B, rank, nd):

@@ -7,16 +7,17 @@ set -u
 N=$1; shift
 LIBS=("$@")
 M=${#LIBS[@]}
+RUN_LOG=$(mktemp); trap 'rm -f "$RUN_LOG"' EXIT  # the current run's output (--full: the per-kernel times)
 mkdir -p gpurun_out
 : > gpurun_out/ab_runs.jsonl
 for i in $(seq 0 $((N - 1))); do
   for j in $(seq 0 $((M - 1))); do
     lib=${LIBS[$(((i + j) % M))]}
     path=${lib%%@*}; envs=(); [ "$path" != "$lib" ] && envs=("${lib#*@}")
-    env "${envs[@]}" CDA_LIB=$path timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-k512-split > gpurun_out/ab_run.log 2>&1 || exit 1
+    env "${envs[@]}" CDA_LIB=$path timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline --no-k512-split > "$RUN_LOG" 2>&1 || exit 1
     python3 -c "
 import json
-for l in open('gpurun_out/ab_run.log'):
+for l in open('$RUN_LOG'):
     if l.startswith('{'):
         d=json.loads(l); print(json.dumps({'lib': '$lib', 'value': d['value'], 'kernels': d['kernels_ms']}))
 " >> gpurun_out/ab_runs.jsonl

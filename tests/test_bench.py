@@ -32,7 +32,7 @@ def _check_ranks(r, n):
 
 
 def test_bench_spawns_two_ranks():
-    r = _run_bench("--gpus", "2", "--dry-run")
+    r = _run_bench("--gpus", "2", "--dry-run", "--full")
     assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["max_rank"] == 1
     _check_ranks(r, 2)
     # config C5's split helper (started before the GPU is touched, run between two CPU barriers) answered
@@ -40,7 +40,7 @@ def test_bench_spawns_two_ranks():
 
 
 def test_bench_spawns_four_ranks():
-    r = _run_bench("--gpus", "4", "--dry-run")
+    r = _run_bench("--gpus", "4", "--dry-run", "--full")
     assert r["n_gpus"] == 4 and r["ranks_seen"] == 4
     _check_ranks(r, 4)
     assert r["k512_split"]["G"] == 4
@@ -49,7 +49,7 @@ def test_bench_spawns_four_ranks():
 def test_bench_spawns_eight_ranks():
     """The driver's N = 8 line: 8 gloo ranks, every rank reports, and config C5's split helper
     answers for G = 8 with its fields (an error field when it fails, never the exit code)."""
-    r = _run_bench("--gpus", "8", "--dry-run")
+    r = _run_bench("--gpus", "8", "--dry-run", "--full")
     assert r["n_gpus"] == 8 and r["ranks_seen"] == 8 and r["max_rank"] == 7
     _check_ranks(r, 8)
     split = r["k512_split"]
@@ -67,6 +67,36 @@ def test_bench_split_helper_failure_is_a_field():
     h.p.wait(timeout=60)
     r = h.run(timeout=5)
     assert "error" in r
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs' writer on host tensors: float .npy files under the budget, the EDS sample the same cells on
+    every call, each sampled cell the buffer's own bytes, roots without the records' padding."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    k, B, w = 4, 6, 8
+    g = torch.Generator().manual_seed(1)
+    eds = torch.randint(0, 256, (B, w * w, 512), dtype=torch.uint8, generator=g)
+    roots = torch.randint(0, 256, (B, 2 * w, 96), dtype=torch.uint8, generator=g)
+    dah = torch.randint(0, 256, (B, 32), dtype=torch.uint8, generator=g)
+    status = torch.full((B,), -1, dtype=torch.int64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 50 * 1000)  # smaller than these outputs: both samplers run
+    runs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), 0, 1, k, B, eds, roots, dah, status)
+        runs.append({f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+        assert sum(os.path.getsize(tmp_path / name / f) for f in runs[-1]) <= 50 * 1000 + 6 * 128
+    a, b = runs
+    assert list(a) == list(b) and all(np.array_equal(a[f], b[f]) for f in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    idx = a["eds_cell_index.npy"].astype(np.int64)
+    assert 0 < len(idx) < B * w * w and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["eds_cells.npy"], eds.view(-1, 512).numpy()[idx].astype(np.float32))
+    blk = a["roots_block_index.npy"].astype(np.int64)
+    assert 0 < len(blk) < B
+    assert np.array_equal(a["roots.npy"], roots.numpy()[blk][:, :, :90].astype(np.float32))
+    assert np.array_equal(a["dah.npy"], dah.numpy().astype(np.float32))
 
 
 def test_cpu_throughput_sampler():
