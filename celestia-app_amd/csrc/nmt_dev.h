@@ -79,21 +79,12 @@ __device__ __forceinline__ void leaf_record(const uint4* sh, uint32_t* A, bool q
   }
 #pragma unroll
   for (int i = 8; i < 16; i++) m[i] = be_window(A[i - 8], A[i - 7], 2);
-  // wave-uniform only (a wave of parity and Q0 cells runs the general path: both paths in one wave cost more than the
-  // 7 rounds saved)
-  if (!CDA_NO_PARITY_MID && __all(!q0)) {
-    uint32_t mw[16], mid[8];
-    mw[0] = 0x00FFFFFFu;
+  // wave-uniform only (a wave of parity and Q0 cells runs all 64 rounds), and one copy of rounds 7..63 for both
+  // cases: in a wave of parity cells m[0..6] already hold the constant words the schedule reads
+  uint32_t mid[8];
 #pragma unroll
-    for (int i = 1; i < 7; i++) mw[i] = 0xFFFFFFFFu;
-#pragma unroll
-    for (int i = 7; i < 16; i++) mw[i] = m[i];
-#pragma unroll
-    for (int i = 0; i < 8; i++) mid[i] = kParityLeafMid7[i];
-    sha256_compress_fenced_from<7, false>(st, mid, mw);
-  } else {
-    sha256_compress(st, m);
-  }
+  for (int i = 0; i < 8; i++) mid[i] = kParityLeafMid7[i];
+  sha256_compress_skip<7>(st, mid, m, !CDA_NO_PARITY_MID && __all(!q0));
   // blocks 1..7: message words 16j..16j+15 = share bytes 64j-30.. : windows of S[16j-8 .. 16j+8].
   // H carries the upper half of the previous 16-word chunk.
   uint32_t H[8];
@@ -220,14 +211,8 @@ __device__ __forceinline__ void ld4(const uint4* p, uint32_t* w) {  // 4 x 16 B 
 // ds_read_b128).  Swizzling the pieces (piece ^ ((lane ^ lane >> 3) & 7)) removed every conflict of the levels 1-2
 // launch (SQ_LDS_BANK_CONFLICT 132 M -> 0) but moved blocks/s by +0.3 / +0.9 % on two boxes (the kernel is
 // VALU-bound): below the 1 % bar, not kept.
-// parity: both children lie in the parity part of the square (every leaf below them has the parity namespace, so each
-// child's first 58 bytes are 0xFF): block 0 is 0x01 ‖ 0xFF x 58 ‖ 5 digest bytes, and its first 14 rounds run on
-// constant words from a constant state -- they are skipped (kParityMid14), 14 of the node's 192 rounds.  About 3 in 4
-// inner nodes of a square are such (rows / columns >= k entirely, the right half of the others).
-constexpr uint32_t kParityMid14[8] = {0xa8abd42b, 0x092979bd, 0x8d5926ca, 0x8df58526,
-                                      0xa812caa9, 0x7cc8da5d, 0x33a85111, 0x7d669380};
 __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, uint4* po, bool store = true,
-                                              uint4* ns_lds = nullptr, bool parity = false) {
+                                              uint4* ns_lds = nullptr) {
   uint32_t st[8], m[16];
   sha256_init(st);
   // message = 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits); 48 words
@@ -241,22 +226,7 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
 #pragma unroll
       for (int i = 0; i < 4; i++) ns_lds[i] = make_uint4(L[4 * i], L[4 * i + 1], L[4 * i + 2], L[4 * i + 3]);
   }
-  // wave-uniform only: a wave whose nodes are partly parity takes the general path (in a divergent wave both paths
-  // would run, 114 rounds instead of 64; measured 3 % slower on the step, profiles/r06_ab_parity_mid.jsonl)
-  if (__all(parity)) {
-    uint32_t mw[16];
-    mw[0] = 0x01FFFFFFu;
-#pragma unroll
-    for (int i = 1; i < 14; i++) mw[i] = 0xFFFFFFFFu;
-    mw[14] = m[14];
-    mw[15] = m[15];
-    uint32_t mid[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) mid[i] = kParityMid14[i];
-    sha256_compress_fenced_from<14>(st, mid, mw);
-  } else {
-    sha256_compress_fenced(st, m);
-  }
+  sha256_compress_fenced(st, m);
   {  // block 1: words 16..31 <- L words 15..22, R words 0..8
     uint32_t L[16], R[16];  // L words 12..27, R words 0..15
     ld4(launder_after(pl, st[0]) + 3, L);  // words 12..27: only 12..23 are read
@@ -317,6 +287,85 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
 #pragma unroll
   for (int i = 8; i < 14; i++) o[i] = S[i];
   o[14] = (S[14] & 0xFFFFu) | (d[0] << 16);
+#pragma unroll
+  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
+  o[22] = d[7] >> 16;
+  o[23] = 0;
+  if (store)
+#pragma unroll
+    for (int i = 0; i < 6; i++) po[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+}
+
+// Inner node whose children both lie in the parity part of the square: every leaf below them has the parity
+// namespace, so each child is 0xFF x 58 ‖ digest ‖ 6 zero bytes.  About 3 in 4 inner nodes of a square are such (rows
+// / columns >= k entirely, the right half of the others).  Only record words 12..23 of each child are read (the
+// digest and the bytes around it; 96 B per node instead of 256), the constant message words are literals and the
+// record's namespace range is 0xFF x 58 without a compare: no LDS parking.  Block 0 is 0x01 ‖ 0xFF x 58 ‖ 5 digest
+// bytes: its first 14 rounds run on constant words from a constant state and are skipped (kParityMid14), 14 of the
+// node's 192 rounds; w23..w36 = 0xFFFFFFFF, w46 = 0, w47 = 1448 fold into the schedules of blocks 1 and 2.
+// For whole waves only: in a wave whose nodes are partly parity both this and hash_node_mem would run (measured 3 %
+// slower on the step with the midstate alone, profiles/r06_ab_parity_mid.jsonl), so callers test __all(parity).
+// Records as pl / pr / po of hash_node_mem (po may equal pl).
+constexpr uint32_t kParityMid14[8] = {0xa8abd42b, 0x092979bd, 0x8d5926ca, 0x8df58526,
+                                      0xa812caa9, 0x7cc8da5d, 0x33a85111, 0x7d669380};
+__device__ __forceinline__ void hash_node_parity(const uint4* pl, const uint4* pr, uint4* po, bool store = true) {
+  uint32_t st[8], m[16];
+  sha256_init(st);
+  // the words are read block by block, each load ordered after the previous compression (as in hash_node_mem)
+  uint32_t L[12];  // L words 12..23: 13..22 are read
+  {  // block 0: 0x01 ‖ 0xFF x 58 ‖ L digest bytes 0..4
+    const uint4 v = launder(pl)[3];
+    L[3] = v.w;
+    m[0] = 0x01FFFFFFu;
+#pragma unroll
+    for (int i = 1; i < 14; i++) m[i] = 0xFFFFFFFFu;
+    m[14] = be_window(v.y, v.z, 3);
+    m[15] = be_window(v.z, v.w, 3);
+    uint32_t mid[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) mid[i] = kParityMid14[i];
+    sha256_compress_fenced_from<14>(st, mid, m);
+  }
+  {
+    const uint4* p = launder_after(pl, st[0]) + 3;
+#pragma unroll
+    for (int i = 1; i < 3; i++) {
+      const uint4 v = p[i];
+      L[4 * i] = v.x, L[4 * i + 1] = v.y, L[4 * i + 2] = v.z, L[4 * i + 3] = v.w;
+    }
+  }
+  // block 1: L digest bytes 5..31 ‖ R's 0xFF x 37
+#pragma unroll
+  for (int i = 0; i < 6; i++) m[i] = be_window(L[3 + i], L[4 + i], 3);  // words 16..21 <- L words 15..21
+  m[6] = be_window(L[9], L[10], 3) | 0xFFu;                              // word 22: L bytes 87..89, R byte 0
+#pragma unroll
+  for (int i = 7; i < 16; i++) m[i] = 0xFFFFFFFFu;
+  sha256_compress_fenced(st, m);
+  uint32_t R[12];  // R words 12..23: 14..23 are read
+  {
+    const uint4* p = launder_after(pr, st[0]) + 3;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const uint4 v = p[i];
+      R[4 * i] = v.x, R[4 * i + 1] = v.y, R[4 * i + 2] = v.z, R[4 * i + 3] = v.w;
+    }
+  }
+  // block 2: R's 0xFF x 21 ‖ R digest ‖ 0x80 ‖ 0.. ‖ len
+#pragma unroll
+  for (int i = 0; i < 5; i++) m[i] = 0xFFFFFFFFu;
+#pragma unroll
+  for (int i = 5; i < 13; i++) m[i] = be_window(R[i - 3], R[i - 2], 1);  // words 37..44 <- R words 14..22
+  m[13] = be_window(R[10], R[11], 1) | 0x00800000u;
+  m[14] = 0;
+  m[15] = 181u * 8u;
+  sha256_compress_fenced(st, m);
+  uint32_t d[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
+  uint32_t o[24];
+#pragma unroll
+  for (int i = 0; i < 14; i++) o[i] = 0xFFFFFFFFu;
+  o[14] = 0xFFFFu | (d[0] << 16);
 #pragma unroll
   for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
   o[22] = d[7] >> 16;

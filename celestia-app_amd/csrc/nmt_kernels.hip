@@ -92,8 +92,8 @@ __global__ void __launch_bounds__(256) nmt_level_kernel(const uint4* __restrict_
 // Leaves (l = 0) are the cell-major leaf records (row_t = w, row_i = 1, col_t = 1, col_i = w); inner
 // levels keep row trees tree-major ([r][i]) and column trees node-major ([i][c]), so that for both
 // kinds the 64 lanes of a wave read 64 adjacent records (row trees: lanes = consecutive i, two
-// children each, 192 contiguous bytes per lane; column trees: lanes = consecutive c) and write 64
-// adjacent records.  The roots land in d_roots[b][0..w) (rows) and [w..2w) (columns).
+// children each, 192 contiguous bytes per lane -- in runs of half a tree where half a tree is under 64 nodes, see
+// the kernel; column trees: lanes = consecutive c) and write 64 adjacent records.  The roots land in d_roots[b][0..w) (rows) and [w..2w) (columns).
 //
 // A thread owns one output node at level l_in + M and computes its whole subtree level by level
 // (2^M - 1 nodes, the intermediate levels written to their level buffers and read back by the same
@@ -115,7 +115,10 @@ __device__ __forceinline__ uint4* level_rec(const LevelDesc& d, unsigned b, bool
   return d.p + off * 6;
 }
 
-__global__ void __launch_bounds__(256) nmt_levels_kernel(LevelSet ls, int log2w, int log2n_out, int M, uint32_t total) {
+// 4 waves per SIMD asked for explicitly: with the general and the digest-only node form both in the level loop the
+// allocator otherwise settles at 130 VGPRs (3 waves per SIMD); held to 128 it still spills no VGPR.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+nmt_levels_kernel(LevelSet ls, int log2w, int log2n_out, int M, uint32_t total) {
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= total) return;
   const unsigned w = 1u << log2w;
@@ -124,9 +127,28 @@ __global__ void __launch_bounds__(256) nmt_levels_kernel(LevelSet ls, int log2w,
   const unsigned rem = gid - b * 2 * per_kind;
   const bool col = rem >= per_kind;
   const unsigned r2 = col ? rem - per_kind : rem;
-  // row trees: node index fastest; column trees: column fastest
-  const unsigned tree = col ? (r2 & (w - 1)) : (r2 >> log2n_out);
-  const unsigned j = col ? (r2 >> log2w) : (r2 & ((1u << log2n_out) - 1));
+  // column trees: column fastest (a wave's nodes are one node index of 64 columns: all parity or none).  Row trees:
+  // node index fastest within a half tree of h = n_out / 2 nodes, then 2^T adjacent trees (2^T x h >= 64 lanes),
+  // then the half, then the remaining tree bits -- so a wave holds left halves only or right halves only (the right
+  // half of every row tree is parity; with the node index fastest over the whole tree, the waves of rows < k were
+  // half Q0-side, half parity and took the general path).  A lane's reads stay one contiguous run of records.
+  unsigned tree, j;
+  if (col) {
+    tree = r2 & (w - 1);
+    j = r2 >> log2w;
+  } else if (log2n_out == 0) {
+    tree = r2;
+    j = 0;
+  } else {
+    const int log2h = log2n_out - 1;
+    const int T = min(max(6 - log2h, 0), log2w);
+    const unsigned jl = r2 & ((1u << log2h) - 1);
+    const unsigned tl = (r2 >> log2h) & ((1u << T) - 1);
+    const unsigned half = (r2 >> (log2h + T)) & 1u;
+    const unsigned th = r2 >> (log2h + T + 1);
+    tree = (th << T) | tl;
+    j = (half << log2h) | jl;
+  }
   __shared__ uint4 s_ns[256 * 8];  // per thread: the first 64 B of both children of the node being hashed
   const unsigned k = w >> 1;
   const int l_in = log2w - log2n_out - M;
@@ -140,8 +162,11 @@ __global__ void __launch_bounds__(256) nmt_levels_kernel(LevelSet ls, int log2w,
 #else
       const bool parity = tree >= k || (i << (l_in + q)) >= k;
 #endif
-      hash_node_mem(level_rec(ls.lv[q - 1], b, col, tree, 2 * i), level_rec(ls.lv[q - 1], b, col, tree, 2 * i + 1),
-                    level_rec(ls.lv[q], b, col, tree, i), true, s_ns + threadIdx.x * 8, parity);
+      const uint4* pl = level_rec(ls.lv[q - 1], b, col, tree, 2 * i);
+      const uint4* pr = level_rec(ls.lv[q - 1], b, col, tree, 2 * i + 1);
+      uint4* po = level_rec(ls.lv[q], b, col, tree, i);
+      if (__all(parity)) hash_node_parity(pl, pr, po);  // wave-uniform: the digest-only form
+      else hash_node_mem(pl, pr, po, true, s_ns + threadIdx.x * 8);
     }
     // the next level reads what this thread just stored
     if (q < M) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -265,6 +265,65 @@ __device__ __forceinline__ void sha256_compress_fenced_from(uint32_t s[8], const
   if (FENCED) __builtin_amdgcn_sched_barrier(0);
 }
 
+// One compression whose rounds 0..START-1 are skipped when `skip` holds: the working state then starts at `mid`, the
+// state after those rounds for the constant words w[0..START) and the chaining input s (precomputed on the host).
+// `skip` must be wave-uniform: it is a scalar branch around the first START rounds, and rounds START..63 exist once
+// for both cases (a second copy of the block for the skipping case held 25 more VGPRs live in the leaf kernel, 144
+// instead of 119: 3 waves per SIMD instead of 4).
+template <int START>
+__device__ __forceinline__ void sha256_compress_skip(uint32_t s[8], const uint32_t (&mid)[8], uint32_t (&w)[16],
+                                                     bool skip) {
+  uint32_t a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
+  if (skip) {
+    a = mid[0], b = mid[1], c = mid[2], d = mid[3], e = mid[4], f = mid[5], g = mid[6], h = mid[7];
+  } else {
+#pragma unroll
+    for (int t = 0; t < START; t++) {
+      const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + w[t];
+      const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
+      h = g;
+      g = f;
+      f = e;
+      e = d + t1;
+      d = c;
+      c = b;
+      b = a;
+      a = t1 + t2;
+    }
+  }
+#pragma unroll
+  for (int t = START; t < 64; t++) {
+    uint32_t wt;
+    if (t < 16) {
+      wt = w[t];
+    } else {
+      const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
+      const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
+      const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
+      wt = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
+      w[t & 15] = wt;
+    }
+    const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + wt;
+    const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
+    h = g;
+    g = f;
+    f = e;
+    e = d + t1;
+    d = c;
+    c = b;
+    b = a;
+    a = t1 + t2;
+  }
+  s[0] += a;
+  s[1] += b;
+  s[2] += c;
+  s[3] += d;
+  s[4] += e;
+  s[5] += f;
+  s[6] += g;
+  s[7] += h;
+}
+
 // Opaque copy of a pointer: loads through it are neither merged with earlier
 // loads of the same address (CSE) nor kept live from them.
 template <typename T>
