@@ -159,6 +159,33 @@ struct TreeSpec {  // a set of trees for launch_tree_roots
   unsigned long long r_stride;
 };
 
+// A launch with more than the default 64 KiB of dynamic LDS needs the kernel's limit raised first: 0, or -1 when that
+// fails; no call at or below 64 KiB.  The limit is a per-device attribute, raised on the current device by each launch
+// that needs it (once per device, as axis_roots_limits() does for its kernels, would be a change in behaviour).
+inline int raise_dynamic_lds(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return 0;
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+}
+
+// Launch plan of the tree kernels that take M levels per launch (nmt_levels_kernel, tree_levels_kernel) over trees of
+// 2^L leaves: the launch that starts from level l_in covers M = 2 levels, or 3 to finish (rather than 2 + 1), and
+// leaves 2^log2n_out nodes per tree.
+struct SubtreeLaunch {
+  int M, log2n_out;
+};
+inline SubtreeLaunch subtree_launch(int L, int l_in) {
+  const int rest = L - l_in;
+  const int M = rest == 3 ? 3 : (rest < 2 ? rest : 2);
+  return {M, rest - M};
+}
+// Records of the inner levels 1 .. l - 1 of `trees` trees of 2^L leaves: where level l starts in a buffer that holds
+// the levels one after the other.
+inline unsigned long long levels_before(unsigned long long trees, int L, int l) {
+  unsigned long long off = 0;
+  for (int q = 1; q < l; q++) off += trees << (L - q);
+  return off;
+}
+
 // profiling hook implemented by the engine
 struct ProfScope {
   void* ctx;

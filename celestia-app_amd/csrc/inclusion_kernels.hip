@@ -122,54 +122,6 @@ __global__ void __launch_bounds__(256) blob_mountain_level_kernel(const BlobDesc
   hash_node_mem(recs + (size_t)g * 6, recs + (size_t)(g + span / 2) * 6, recs + (size_t)g * 6);
 }
 
-// SHA256(0x00 ‖ node[0..90)) of a 96-B record: the RFC-6962 leaf hash of an NMT node.
-__device__ __forceinline__ void leaf90_digest(const uint4* rec, uint32_t* st) {
-  uint32_t L[24];
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    const uint4 v = rec[i];
-    L[4 * i] = v.x;
-    L[4 * i + 1] = v.y;
-    L[4 * i + 2] = v.z;
-    L[4 * i + 3] = v.w;
-  }
-  uint32_t m[16];
-  sha256_init(st);
-  m[0] = be_window(0u, L[0], 3);
-#pragma unroll
-  for (int t = 1; t < 16; t++) m[t] = be_window(L[t - 1], L[t], 3);
-  sha256_compress(st, m);
-#pragma unroll
-  for (int t = 0; t < 16; t++) {
-    const int wi = 16 + t;
-    if (wi <= 21) m[t] = be_window(L[wi - 1], L[wi], 3);
-    else if (wi == 22) m[t] = be_window(L[21], L[22], 3) | 0x80u;
-    else if (wi < 31) m[t] = 0;
-    else m[t] = 91u * 8u;
-  }
-  sha256_compress(st, m);
-}
-
-// SHA256(0x01 ‖ L ‖ R) of two digests held as big-endian words.
-__device__ __forceinline__ void inner_digest(const uint32_t* Ld, const uint32_t* Rd, uint32_t* o) {
-  uint32_t st[8], m[16];
-  sha256_init(st);
-  m[0] = 0x01000000u | (Ld[0] >> 8);
-#pragma unroll
-  for (int t = 1; t < 8; t++) m[t] = (Ld[t - 1] << 24) | (Ld[t] >> 8);
-  m[8] = (Ld[7] << 24) | (Rd[0] >> 8);
-#pragma unroll
-  for (int t = 9; t < 16; t++) m[t] = (Rd[t - 9] << 24) | (Rd[t - 8] >> 8);
-  sha256_compress(st, m);
-  m[0] = (Rd[7] << 24) | 0x00800000u;
-#pragma unroll
-  for (int t = 1; t < 15; t++) m[t] = 0;
-  m[15] = 65u * 8u;
-  sha256_compress(st, m);
-#pragma unroll
-  for (int t = 0; t < 8; t++) o[t] = st[t];
-}
-
 // One workgroup per set.  Levels pair (2i, 2i+1) and promote an odd last node,
 // the same tree as HashFromByteSlices' split at the largest power of two below n.
 __global__ void __launch_bounds__(256) merkle_sets_kernel(const uint4* __restrict__ recs,
@@ -185,8 +137,9 @@ __global__ void __launch_bounds__(256) merkle_sets_kernel(const uint4* __restric
   }
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const uint32_t r = idx ? idx[b0 + i] : b0 + (uint32_t)i;
-    uint32_t st[8];
-    leaf90_digest(recs + (size_t)r * 6, st);
+    uint32_t L[24], st[8];
+    load_rec(recs + (size_t)r * 6, L);
+    dah_leaf_digest(L, st);  // SHA256(0x00 ‖ node[0..90)): the RFC-6962 leaf hash of an NMT node
 #pragma unroll
     for (int t = 0; t < 8; t++) sdig[i * 8 + t] = st[t];
     if (nodes_out) {
@@ -200,19 +153,7 @@ __global__ void __launch_bounds__(256) merkle_sets_kernel(const uint4* __restric
   size_t base = (size_t)n;
   for (int cnt = n; cnt > 1;) {
     const int oc = (cnt + 1) >> 1;
-    for (int i = threadIdx.x; i < oc; i += blockDim.x) {
-      uint32_t* o = dst + i * 8;
-      if (2 * i + 1 < cnt) {
-        inner_digest(src + 2 * i * 8, src + (2 * i + 1) * 8, o);
-      } else {
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[t] = src[2 * i * 8 + t];
-      }
-      if (nodes_out) {
-#pragma unroll
-        for (int t = 0; t < 8; t++) nodes_out[(base + i) * 8 + t] = bswap(o[t]);
-      }
-    }
+    rfc_level_wide(src, dst, cnt, nodes_out ? nodes_out + base * 8 : nullptr);
     __syncthreads();
     uint32_t* tmp = src;
     src = dst;
@@ -285,9 +226,7 @@ int launch_merkle_sets(const void* d_recs, const uint32_t* d_idx, const uint32_t
   if (nsets <= 0) return 0;
   const size_t lds = ((size_t)max_set + (max_set + 1) / 2) * 32;
   if (lds > 160 * 1024) return -2;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)merkle_sets_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return -1;
+  if (raise_dynamic_lds((const void*)merkle_sets_kernel, lds)) return -1;
   hipLaunchKernelGGL(merkle_sets_kernel, dim3(nsets), dim3(256), lds ? lds : 32, s, (const uint4*)d_recs, d_idx, d_off,
                      (uint32_t*)d_out, (uint32_t*)d_nodes_out);
   return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -1,5 +1,6 @@
-// nmt_dev.h — erasured-NMT leaf hashing device code (leaf_hash_kernel and the
-// single-tree / axis-list leaf kernels in nmt_kernels.hip).
+// nmt_dev.h — device building blocks of the NMT and RFC-6962 hash kernels (nmt_kernels.hip, split_kernels.hip,
+// inclusion_kernels.hip): the leaf message and record, the inner node in its three forms, 96-B records to and from
+// registers, the push-order compare, RFC-6962 digests and levels, and the level loops several kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,10 +10,7 @@
 
 namespace cda {
 
-// ---------------------------------------------------------------------------
-// Leaf hashing: one thread per EDS cell.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void load16(const uint4* p, uint32_t* w) {
+__device__ __forceinline__ void load16(const uint4* p, uint32_t* w) {  // 4 x 16 B -> 16 words
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     uint4 v = p[i];
@@ -21,6 +19,21 @@ __device__ __forceinline__ void load16(const uint4* p, uint32_t* w) {
     w[4 * i + 2] = v.z;
     w[4 * i + 3] = v.w;
   }
+}
+// A 96-B record (6 x 16 B) to and from its 24 words
+__device__ __forceinline__ void load_rec(const uint4* p, uint32_t (&r)[24]) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const uint4 v = p[i];
+    r[4 * i + 0] = v.x;
+    r[4 * i + 1] = v.y;
+    r[4 * i + 2] = v.z;
+    r[4 * i + 3] = v.w;
+  }
+}
+__device__ __forceinline__ void store_rec(uint4* p, const uint32_t (&o)[24]) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) p[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
 }
 
 // Big-endian namespace words of a 29-byte namespace held little-endian in n[0..7]
@@ -37,7 +50,18 @@ __device__ __forceinline__ int ns_cmp(const uint32_t* a, const uint32_t* b) {
   }
   return 0;
 }
+// Push order (nmt ErrInvalidPushOrder): whether the share or leaf record at `next` has a smaller namespace than the
+// one whose first words are in A.  Callers test Q0 neighbours only: parity leaves carry 0xFF x 29, the maximum.
+__device__ __forceinline__ bool ns_below(const uint4* next, const uint32_t* A) {
+  const uint4 v0 = next[0], v1 = next[1];
+  const uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+  return ns_cmp(nb, A) < 0;
+}
 
+// ---------------------------------------------------------------------------
+// Leaf hashing: one thread per share.  The message is 0x00 ‖ ns ‖ share (542 bytes, 9 blocks), the record
+// ns ‖ ns ‖ SHA256(message) ‖ 6 zero bytes, ns = share[0:29] if q0 else 0xFF x 29.
+// ---------------------------------------------------------------------------
 // A parity leaf's first block starts 0x00 ‖ 0xFF x 29 (message words 0..6 constant): its working state after rounds
 // 0..6 is a constant, so those rounds are skipped (3 in 4 cells of a square are parity leaves).
 constexpr uint32_t kParityLeafMid7[8] = {0x1ca5c518, 0x33e5c969, 0xbd2d00ce, 0xa4502bae,
@@ -46,25 +70,8 @@ constexpr uint32_t kParityLeafMid7[8] = {0x1ca5c518, 0x33e5c969, 0xbd2d00ce, 0xa
 #define CDA_NO_PARITY_MID 0  // diagnostic A/B: every leaf and inner node through all 64 rounds of its first block
 #endif
 
-// Leaf record of one 512-B share whose first 64 bytes are already in A[0..16):
-// ns ‖ ns ‖ SHA256(0x00 ‖ ns ‖ share) ‖ 6 zero bytes, ns = share[0:29] if q0 else 0xFF×29.
-// Blocks 1..7 stay a loop (one copy of the compression code: measured as fast as
-// the unrolled form on MI355X, with half the instruction footprint).
-// The share is read one 128-B line at a time (two 64-B chunks loaded together, the odd chunk held in N until its
-// block): loaded a compression apart, the line's second half missed in L2 often enough that the leaf kernel fetched
-// 1.31x its bytes (all 128-B requests, profiles/r04_rdreq_sizes.json).  PAIRS = false: one chunk per block (16
-// fewer VGPRs; repair's root check, whose kernel would otherwise pass 128).
-template <bool PAIRS = true>
-__device__ __forceinline__ void leaf_record(const uint4* sh, uint32_t* A, bool q0, uint4* out) {
-  uint32_t N[16];
-  if (PAIRS) load16(sh + 4, N);  // chunk 1, the rest of the line A came from
-  uint32_t ns[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) ns[i] = q0 ? A[i] : 0xFFFFFFFFu;
-  uint32_t st[8];
-  sha256_init(st);
-  uint32_t m[16];
-  // block 0: 0x00 ‖ ns[0..29) ‖ share[0..34)
+// Block 0 from the first 64 share bytes A: 0x00 ‖ ns[0..29) ‖ share[0..34)
+__device__ __forceinline__ void leaf_block0_words(const uint32_t (&A)[16], bool q0, uint32_t (&m)[16]) {
   if (q0) {
     m[0] = be_window(0u, A[0], 3);
 #pragma unroll
@@ -79,15 +86,84 @@ __device__ __forceinline__ void leaf_record(const uint4* sh, uint32_t* A, bool q
   }
 #pragma unroll
   for (int i = 8; i < 16; i++) m[i] = be_window(A[i - 8], A[i - 7], 2);
+}
+// Block j (1..8) holds share bytes 64j - 30 .. 64j + 33: windows of H = share words 16j - 8 .. 16j - 1 and
+// C = share words 16j .. 16j + 15.  The last block (j = 8, no C) ends the message: share bytes 482..511, 0x80,
+// zeros, the bit length.
+__device__ __forceinline__ void leaf_block_words(const uint32_t* H, const uint32_t* C, bool last, uint32_t (&m)[16]) {
+#pragma unroll
+  for (int i = 0; i < 7; i++) m[i] = be_window(H[i], H[i + 1], 2);
+  if (!last) {
+    m[7] = be_window(H[7], C[0], 2);
+#pragma unroll
+    for (int i = 8; i < 16; i++) m[i] = be_window(C[i - 8], C[i - 7], 2);
+  } else {
+    m[7] = be_window(H[7], 0x80u, 2);
+#pragma unroll
+    for (int i = 8; i < 15; i++) m[i] = 0;
+    m[15] = 542u * 8u;
+  }
+}
+// Block j (1..8) read from the share itself (C stays unread, and is not loaded, for the last block)
+__device__ __forceinline__ void leaf_block_words(const uint4* sh, int j, uint32_t (&m)[16]) {
+  uint32_t H[8], C[16];
+  {
+    const uint4 a = sh[4 * j - 2], b = sh[4 * j - 1];
+    H[0] = a.x, H[1] = a.y, H[2] = a.z, H[3] = a.w, H[4] = b.x, H[5] = b.y, H[6] = b.z, H[7] = b.w;
+  }
+  const bool last = !(j < 8);
+  if (!last) load16(sh + 4 * j, C);
+  leaf_block_words(H, C, last, m);
+}
+
+// Words 14..23 of a record: the namespace range's last two bytes (the low half of w14) ‖ the digest of the final
+// state st ‖ 6 zero bytes
+__device__ __forceinline__ void rec_digest_words(uint32_t w14, const uint32_t* st, uint32_t (&o)[24]) {
+  uint32_t d[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
+  o[14] = (w14 & 0xFFFFu) | (d[0] << 16);
+#pragma unroll
+  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
+  o[22] = d[7] >> 16;
+  o[23] = 0;
+}
+
+// The leaf record from the final state
+__device__ __forceinline__ void leaf_record_out(const uint32_t (&A)[16], bool q0, const uint32_t (&st)[8], uint4* out) {
+  uint32_t ns[8], o[24];
+#pragma unroll
+  for (int i = 0; i < 8; i++) ns[i] = q0 ? A[i] : 0xFFFFFFFFu;
+#pragma unroll
+  for (int i = 0; i < 7; i++) o[i] = ns[i];
+  o[7] = (ns[7] & 0xFFu) | (ns[0] << 8);
+#pragma unroll
+  for (int i = 8; i < 14; i++) o[i] = le_window(ns[i - 8], ns[i - 7], 3);
+  rec_digest_words(le_window(ns[6], ns[7], 3), st, o);
+  store_rec(out, o);
+}
+
+// Leaf record of one 512-B share whose first 64 bytes are already in A.
+// Blocks 1..7 stay a loop (one copy of the compression code: measured as fast as
+// the unrolled form on MI355X, with half the instruction footprint).
+// The share is read one 128-B line at a time (two 64-B chunks loaded together, the odd chunk held in N until its
+// block): loaded a compression apart, the line's second half missed in L2 often enough that the leaf kernel fetched
+// 1.31x its bytes (all 128-B requests, profiles/r04_rdreq_sizes.json).  PAIRS = false: one chunk per block (16
+// fewer VGPRs; repair's root check, whose kernel would otherwise pass 128).
+template <bool PAIRS = true>
+__device__ __forceinline__ void leaf_record(const uint4* sh, const uint32_t (&A)[16], bool q0, uint4* out) {
+  uint32_t N[16];
+  if (PAIRS) load16(sh + 4, N);  // chunk 1, the rest of the line A came from
+  uint32_t st[8], m[16];
+  sha256_init(st);
+  leaf_block0_words(A, q0, m);
   // wave-uniform only (a wave of parity and Q0 cells runs all 64 rounds), and one copy of rounds 7..63 for both
   // cases: in a wave of parity cells m[0..6] already hold the constant words the schedule reads
   uint32_t mid[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) mid[i] = kParityLeafMid7[i];
   sha256_compress_skip<7>(st, mid, m, !CDA_NO_PARITY_MID && __all(!q0));
-  // blocks 1..7: message words 16j..16j+15 = share bytes 64j-30.. : windows of S[16j-8 .. 16j+8].
-  // H carries the upper half of the previous 16-word chunk.
-  uint32_t H[8];
+  uint32_t H[8];  // the upper half of the previous 16-word chunk
 #pragma unroll
   for (int i = 0; i < 8; i++) H[i] = A[8 + i];
 #pragma unroll 1
@@ -102,40 +178,14 @@ __device__ __forceinline__ void leaf_record(const uint4* sh, uint32_t* A, bool q
       load16(sh + 4 * j, C);
       load16(sh + 4 * (j + 1), N);
     }
-#pragma unroll
-    for (int i = 0; i < 7; i++) m[i] = be_window(H[i], H[i + 1], 2);
-    m[7] = be_window(H[7], C[0], 2);
-#pragma unroll
-    for (int i = 8; i < 16; i++) m[i] = be_window(C[i - 8], C[i - 7], 2);
+    leaf_block_words(H, C, false, m);
     sha256_compress(st, m);
 #pragma unroll
     for (int i = 0; i < 8; i++) H[i] = C[8 + i];
   }
-  // block 8: share bytes 482..511, 0x80, zeros, bit length 542*8
-#pragma unroll
-  for (int i = 0; i < 7; i++) m[i] = be_window(H[i], H[i + 1], 2);
-  m[7] = be_window(H[7], 0x80u, 2);
-#pragma unroll
-  for (int i = 8; i < 15; i++) m[i] = 0;
-  m[15] = 542u * 8u;
+  leaf_block_words(H, nullptr, true, m);
   sha256_compress(st, m);
-  // record: ns ‖ ns ‖ digest ‖ 6 zero bytes
-  uint32_t d[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
-  uint32_t o[24];
-#pragma unroll
-  for (int i = 0; i < 7; i++) o[i] = ns[i];
-  o[7] = (ns[7] & 0xFFu) | (ns[0] << 8);
-#pragma unroll
-  for (int i = 8; i < 14; i++) o[i] = le_window(ns[i - 8], ns[i - 7], 3);
-  o[14] = (le_window(ns[6], ns[7], 3) & 0xFFFFu) | (d[0] << 16);
-#pragma unroll
-  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
-  o[22] = d[7] >> 16;
-  o[23] = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) out[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+  leaf_record_out(A, q0, st, out);
 }
 
 // One EDS cell `gid` (= blk * w^2 + r * w + c) of a batch: push-order check against
@@ -151,34 +201,14 @@ __device__ __forceinline__ void leaf_cell(const uint8_t* __restrict__ eds, uint4
 
   uint32_t A[16];
   load16(sh, A);
-  uint32_t ns[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) ns[i] = A[i];
-
-  // Namespace order (nmt Push ErrInvalidPushOrder) — checked for Q0 neighbours;
-  // parity leaves carry 0xFF×29, the maximum, so only Q0 pairs can violate it.
   if (q0) {
-    if (c + 1 < k) {
-      uint32_t nb[8];
-      const uint4* p = reinterpret_cast<const uint4*>(eds + ((size_t)gid + 1) * CDA_SHARE);
-      uint4 v0 = p[0], v1 = p[1];
-      nb[0] = v0.x; nb[1] = v0.y; nb[2] = v0.z; nb[3] = v0.w;
-      nb[4] = v1.x; nb[5] = v1.y; nb[6] = v1.z; nb[7] = v1.w;
-      if (ns_cmp(nb, ns) < 0) {
-        unsigned long long key = ((unsigned long long)CDA_AXIS_ROW << 40) | ((unsigned long long)r << 20) | (c + 1);
-        atomicMin(status + blk, key);
-      }
+    if (c + 1 < k && ns_below(sh + CDA_SHARE / 16, A)) {
+      unsigned long long key = ((unsigned long long)CDA_AXIS_ROW << 40) | ((unsigned long long)r << 20) | (c + 1);
+      atomicMin(status + blk, key);
     }
-    if (r + 1 < k) {
-      uint32_t nb[8];
-      const uint4* p = reinterpret_cast<const uint4*>(eds + ((size_t)gid + w) * CDA_SHARE);
-      uint4 v0 = p[0], v1 = p[1];
-      nb[0] = v0.x; nb[1] = v0.y; nb[2] = v0.z; nb[3] = v0.w;
-      nb[4] = v1.x; nb[5] = v1.y; nb[6] = v1.z; nb[7] = v1.w;
-      if (ns_cmp(nb, ns) < 0) {
-        unsigned long long key = ((unsigned long long)CDA_AXIS_COL << 40) | ((unsigned long long)c << 20) | (r + 1);
-        atomicMin(status + blk, key);
-      }
+    if (r + 1 < k && ns_below(sh + (size_t)w * (CDA_SHARE / 16), A)) {
+      unsigned long long key = ((unsigned long long)CDA_AXIS_COL << 40) | ((unsigned long long)c << 20) | (r + 1);
+      atomicMin(status + blk, key);
     }
   }
 
@@ -188,15 +218,23 @@ __device__ __forceinline__ void leaf_cell(const uint8_t* __restrict__ eds, uint4
 // ---------------------------------------------------------------------------
 // Inner NMT node (also the in-place mountain fold of inclusion_kernels.hip).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void ld4(const uint4* p, uint32_t* w) {  // 4 x 16 B -> 16 words
+// The node record from words 0..14 of both children (their namespace ranges) and the digest state:
+// min = L.min; max = R.min == parity ns ? L.max : R.max.
+__device__ __forceinline__ void node_record(const uint32_t* L, const uint32_t* R, const uint32_t (&st)[8],
+                                            uint32_t (&o)[24]) {
+  bool rmin_max = true;
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint4 v = p[i];
-    w[4 * i + 0] = v.x;
-    w[4 * i + 1] = v.y;
-    w[4 * i + 2] = v.z;
-    w[4 * i + 3] = v.w;
-  }
+  for (int i = 0; i < 7; i++) rmin_max &= (R[i] == 0xFFFFFFFFu);
+  rmin_max &= ((R[7] & 0xFFu) == 0xFFu);
+  uint32_t S[16];
+#pragma unroll
+  for (int i = 7; i < 15; i++) S[i] = rmin_max ? L[i] : R[i];
+#pragma unroll
+  for (int i = 0; i < 7; i++) o[i] = L[i];
+  o[7] = (L[7] & 0xFFu) | (S[7] & 0xFFFFFF00u);
+#pragma unroll
+  for (int i = 8; i < 14; i++) o[i] = S[i];
+  rec_digest_words(S[14], st, o);
 }
 
 // Inner node from the two child records at pl / pr, written to po (po may equal
@@ -218,7 +256,7 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
   // message = 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits); 48 words
   {  // block 0: words 0..15 <- L words 0..15
     uint32_t L[16];
-    ld4(launder(pl), L);
+    load16(launder(pl), L);
     m[0] = be_window(0x01000000u, L[0], 3);
 #pragma unroll
     for (int i = 1; i < 16; i++) m[i] = be_window(L[i - 1], L[i], 3);
@@ -229,8 +267,8 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
   sha256_compress_fenced(st, m);
   {  // block 1: words 16..31 <- L words 15..22, R words 0..8
     uint32_t L[16], R[16];  // L words 12..27, R words 0..15
-    ld4(launder_after(pl, st[0]) + 3, L);  // words 12..27: only 12..23 are read
-    ld4(launder_after(pr, st[0]), R);      // words 0..15: only 0..11 are read
+    load16(launder_after(pl, st[0]) + 3, L);  // words 12..27: only 12..23 are read
+    load16(launder_after(pr, st[0]), R);      // words 0..15: only 0..11 are read
     if (ns_lds)
 #pragma unroll
       for (int i = 0; i < 4; i++) ns_lds[4 + i] = make_uint4(R[4 * i], R[4 * i + 1], R[4 * i + 2], R[4 * i + 3]);
@@ -245,7 +283,7 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
   sha256_compress_fenced(st, m);
   {  // block 2: words 32..47 <- R words 8..23
     uint32_t R[16];
-    ld4(launder_after(pr, st[0]) + 2, R);
+    load16(launder_after(pr, st[0]) + 2, R);
 #pragma unroll
     for (int i = 0; i < 16; i++) {
       const int wi = 32 + i;
@@ -257,43 +295,22 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
   }
   sha256_compress_fenced(st, m);
 
-  // namespace range: min = L.min; max = R.min == parity ns ? L.max : R.max
+  // the namespace range comes from the children's first 16 words, read again
   uint32_t L[16], R[16];
   if (ns_lds) {
     uint32_t z = 0;  // an offset tied to the last compression keeps the LDS reads below it (pointer stays in LDS)
     asm volatile("" : "+v"(z) : "v"(st[0]));
-    ld4(ns_lds + z, L);
-    ld4(ns_lds + z + 4, R);
+    load16(ns_lds + z, L);
+    load16(ns_lds + z + 4, R);
 #pragma unroll
     for (int i = 0; i < 16; i++) asm volatile("" : "+v"(L[i]), "+v"(R[i]));  // values, not a select of addresses
   } else {
-    ld4(launder_after(pl, st[0]), L);
-    ld4(launder_after(pr, st[0]), R);
+    load16(launder_after(pl, st[0]), L);
+    load16(launder_after(pr, st[0]), R);
   }
-  bool rmin_max = true;
-#pragma unroll
-  for (int i = 0; i < 7; i++) rmin_max &= (R[i] == 0xFFFFFFFFu);
-  rmin_max &= ((R[7] & 0xFFu) == 0xFFu);
-  uint32_t S[16];
-#pragma unroll
-  for (int i = 7; i < 15; i++) S[i] = rmin_max ? L[i] : R[i];
-  uint32_t d[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
   uint32_t o[24];
-#pragma unroll
-  for (int i = 0; i < 7; i++) o[i] = L[i];
-  o[7] = (L[7] & 0xFFu) | (S[7] & 0xFFFFFF00u);
-#pragma unroll
-  for (int i = 8; i < 14; i++) o[i] = S[i];
-  o[14] = (S[14] & 0xFFFFu) | (d[0] << 16);
-#pragma unroll
-  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
-  o[22] = d[7] >> 16;
-  o[23] = 0;
-  if (store)
-#pragma unroll
-    for (int i = 0; i < 6; i++) po[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+  node_record(L, R, st, o);
+  if (store) store_rec(po, o);
 }
 
 // Inner node whose children both lie in the parity part of the square: every leaf below them has the parity
@@ -359,20 +376,11 @@ __device__ __forceinline__ void hash_node_parity(const uint4* pl, const uint4* p
   m[14] = 0;
   m[15] = 181u * 8u;
   sha256_compress_fenced(st, m);
-  uint32_t d[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
   uint32_t o[24];
 #pragma unroll
   for (int i = 0; i < 14; i++) o[i] = 0xFFFFFFFFu;
-  o[14] = 0xFFFFu | (d[0] << 16);
-#pragma unroll
-  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
-  o[22] = d[7] >> 16;
-  o[23] = 0;
-  if (store)
-#pragma unroll
-    for (int i = 0; i < 6; i++) po[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+  rec_digest_words(0xFFFFu, st, o);
+  if (store) store_rec(po, o);
 }
 
 // Message block B (0..2) of an inner node: 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits), children in
@@ -391,10 +399,6 @@ __device__ __forceinline__ void node_block(const uint32_t (&L)[24], const uint32
     else m[i] = 181u * 8u;
   }
 }
-// The node record from its children and the digest state: min = L.min; max = R.min == parity ns ? L.max : R.max.
-__device__ __forceinline__ void node_record(const uint32_t (&L)[24], const uint32_t (&R)[24], const uint32_t (&st)[8],
-                                            uint32_t (&o)[24]);
-
 // hash_node_mem with both children already in registers (24 words each, record layout): the form for latency
 // kernels that run one wave per SIMD, where registers are free and a memory round trip per compression is not.
 __device__ __forceinline__ void hash_node_regs(const uint32_t (&L)[24], const uint32_t (&R)[24], uint32_t (&o)[24]) {
@@ -408,28 +412,87 @@ __device__ __forceinline__ void hash_node_regs(const uint32_t (&L)[24], const ui
   sha256_compress(st, m);
   node_record(L, R, st, o);
 }
-__device__ __forceinline__ void node_record(const uint32_t (&L)[24], const uint32_t (&R)[24], const uint32_t (&st)[8],
-                                            uint32_t (&o)[24]) {
-  bool rmin_max = true;
+
+// A tree folded in place in LDS: node i of level l sits at slot i << l of lnodes (a last odd node keeps its slot,
+// which is the nmt split at the largest power of two below n).  lds_node_mem hashes one node from its two children
+// at level l - 1; lds_level_mem the level's `pairs` nodes by the whole workgroup.
+__device__ __forceinline__ void lds_node_mem(uint4* lnodes, int l, int i, bool store = true) {
+  hash_node_mem(lnodes + ((size_t)(2 * i) << (l - 1)) * 6, lnodes + ((size_t)(2 * i + 1) << (l - 1)) * 6,
+                lnodes + ((size_t)i << l) * 6, store);
+}
+__device__ __forceinline__ void lds_level_mem(uint4* lnodes, int l, int pairs) {
+  for (int i = threadIdx.x; i < pairs; i += blockDim.x) lds_node_mem(lnodes, l, i);
+}
+
+// ---------------------------------------------------------------------------
+// RFC-6962 (merkle.HashFromByteSlices) over NMT nodes; digests are 8 big-endian words.
+// ---------------------------------------------------------------------------
+// Leaf digest SHA256(0x00 ‖ record[0..90)) of a node record; message block B of it
+template <int B>
+__device__ __forceinline__ void dah_leaf_block(const uint32_t (&L)[24], uint32_t (&m)[16]) {
+  // 0x00 ‖ root[0..90) ‖ 0x80 ‖ ... ‖ len(91*8)
 #pragma unroll
-  for (int i = 0; i < 7; i++) rmin_max &= (R[i] == 0xFFFFFFFFu);
-  rmin_max &= ((R[7] & 0xFFu) == 0xFFu);
-  uint32_t S[16];
+  for (int t = 0; t < 16; t++) {
+    const int wi = 16 * B + t;
+    if (wi == 0) m[t] = be_window(0u, L[0], 3);
+    else if (wi <= 21) m[t] = be_window(L[wi - 1], L[wi], 3);
+    else if (wi == 22) m[t] = be_window(L[21], L[22], 3) | 0x80u;
+    else if (wi < 31) m[t] = 0;
+    else m[t] = 91u * 8u;
+  }
+}
+__device__ __forceinline__ void dah_leaf_digest(const uint32_t (&L)[24], uint32_t (&st)[8]) {
+  uint32_t m[16];
+  sha256_init(st);
+  dah_leaf_block<0>(L, m);
+  sha256_compress(st, m);
+  dah_leaf_block<1>(L, m);
+  sha256_compress(st, m);
+}
+// Inner node message block B of digests Ld, Rd: 0x01 ‖ Ld ‖ Rd ‖ pad, 65 bytes
+template <int B>
+__device__ __forceinline__ void rfc_node_block(const uint32_t* Ld, const uint32_t* Rd, uint32_t (&m)[16]) {
+  if (B == 0) {
+    m[0] = 0x01000000u | (Ld[0] >> 8);
 #pragma unroll
-  for (int i = 7; i < 15; i++) S[i] = rmin_max ? L[i] : R[i];
-  uint32_t d[8];
+    for (int t = 1; t < 8; t++) m[t] = (Ld[t - 1] << 24) | (Ld[t] >> 8);
+    m[8] = (Ld[7] << 24) | (Rd[0] >> 8);
 #pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
+    for (int t = 9; t < 16; t++) m[t] = (Rd[t - 9] << 24) | (Rd[t - 8] >> 8);
+  } else {
+    m[0] = (Rd[7] << 24) | 0x00800000u;
 #pragma unroll
-  for (int i = 0; i < 7; i++) o[i] = L[i];
-  o[7] = (L[7] & 0xFFu) | (S[7] & 0xFFFFFF00u);
+    for (int t = 1; t < 15; t++) m[t] = 0;
+    m[15] = 65u * 8u;
+  }
+}
+// One level by the whole workgroup, a node per thread: the cnt digests at src to (cnt + 1) / 2 at dst.  Levels pair
+// (2i, 2i+1) and promote an odd last node, which is the same tree as HashFromByteSlices' "split at the largest power
+// of two below n" recursion.  nodes_out (optional): the level's digests as bytes, node i at nodes_out + 32 i.
+__device__ __forceinline__ void rfc_level_wide(const uint32_t* src, uint32_t* dst, int cnt, uint32_t* nodes_out) {
+  const int out_cnt = (cnt + 1) >> 1;
+  for (int i = threadIdx.x; i < out_cnt; i += blockDim.x) {
+    uint32_t* o = dst + i * 8;
+    const uint32_t* Ld = src + (2 * i) * 8;
+    if (2 * i + 1 < cnt) {
+      const uint32_t* Rd = src + (2 * i + 1) * 8;
+      uint32_t st[8], m[16];
+      sha256_init(st);
+      rfc_node_block<0>(Ld, Rd, m);
+      sha256_compress(st, m);
+      rfc_node_block<1>(Ld, Rd, m);
+      sha256_compress(st, m);
 #pragma unroll
-  for (int i = 8; i < 14; i++) o[i] = S[i];
-  o[14] = (S[14] & 0xFFFFu) | (d[0] << 16);
+      for (int t = 0; t < 8; t++) o[t] = st[t];
+    } else {
 #pragma unroll
-  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
-  o[22] = d[7] >> 16;
-  o[23] = 0;
+      for (int t = 0; t < 8; t++) o[t] = Ld[t];
+    }
+    if (nodes_out) {
+#pragma unroll
+      for (int t = 0; t < 8; t++) nodes_out[(size_t)i * 8 + t] = bswap(o[t]);
+    }
+  }
 }
 
 }  // namespace cda

@@ -25,6 +25,7 @@
 #include <set>
 
 #include "cda_internal.h"
+#include "ctx.h"
 #include "nmt_dev.h"
 #include "sha256_dev.h"
 
@@ -36,20 +37,6 @@ __global__ void __launch_bounds__(256) leaf_hash_kernel(const uint8_t* __restric
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= total_cells) return;
   leaf_cell(eds, nodes, status, k, log2w, gid);
-}
-
-// ---------------------------------------------------------------------------
-// Inner NMT node.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void load_node(const uint4* p, uint32_t* n) {
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    uint4 v = p[i];
-    n[4 * i + 0] = v.x;
-    n[4 * i + 1] = v.y;
-    n[4 * i + 2] = v.z;
-    n[4 * i + 3] = v.w;
-  }
 }
 
 // One thread per output node. Level 1 reads leaf records in cell-major layout
@@ -178,8 +165,8 @@ nmt_levels_kernel(LevelSet ls, int log2w, int log2n_out, int M, uint32_t total) 
 int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k, int nblocks, hipStream_t s,
                      void* prof_ctx) {
   const int w = 2 * k;
-  int L = 0;
-  while ((1 << L) < w) L++;
+  if (k < 1) return -2;
+  const int L = ilog2i(w);
   if ((1 << L) != w || L < 1) return -2;
   auto desc = [&](int l) {
     LevelDesc d{};
@@ -193,20 +180,16 @@ int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k,
       d.blk = 2ull * w;
       d.row0 = 0, d.row_t = 1, d.row_i = 0, d.col0 = w, d.col_t = 1, d.col_i = 0;
     } else {
-      unsigned long long off = 0;  // levels 1 .. l-1 before this one
-      for (int q = 1; q < l; q++) off += 2ull * w * (w >> q);
-      d.p = (uint4*)d_levels + off * (unsigned long long)nblocks * 6;
+      d.p = (uint4*)d_levels + levels_before(2ull * w, L, l) * (unsigned long long)nblocks * 6;
       d.blk = 2ull * w * n;
       d.row0 = 0, d.row_t = n, d.row_i = 1, d.col0 = w * n, d.col_t = 1, d.col_i = w;
     }
     return d;
   };
   for (int l_in = 0; l_in < L;) {
-    int M = std::min(2, L - l_in);
-    if (L - l_in == 3) M = 3;  // finish with one 3-level launch rather than 2 + 1
+    const auto [M, log2n_out] = subtree_launch(L, l_in);
     LevelSet ls{};
     for (int q = 0; q <= M; q++) ls.lv[q] = desc(l_in + q);
-    const int log2n_out = L - (l_in + M);
     const uint32_t total = (uint32_t)nblocks * 2u * ((uint32_t)w << log2n_out);
     {
       ProfScope ps(prof_ctx, l_in == 0 ? "nmt_levels_1" : "nmt_levels", s);
@@ -223,49 +206,8 @@ int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k,
 // Levels pair (2i, 2i+1) and promote an odd last node, which is the same tree as
 // HashFromByteSlices' "split at the largest power of two below n" recursion.
 // ---------------------------------------------------------------------------
-// DAH leaf digest: SHA256(0x00 || root record[0..90)) as 8 big-endian words; message block B of it
-template <int B>
-__device__ __forceinline__ void dah_leaf_block(const uint32_t (&L)[24], uint32_t (&m)[16]) {
-  // 0x00 ‖ root[0..90) ‖ 0x80 ‖ ... ‖ len(91*8)
-#pragma unroll
-  for (int t = 0; t < 16; t++) {
-    const int wi = 16 * B + t;
-    if (wi == 0) m[t] = be_window(0u, L[0], 3);
-    else if (wi <= 21) m[t] = be_window(L[wi - 1], L[wi], 3);
-    else if (wi == 22) m[t] = be_window(L[21], L[22], 3) | 0x80u;
-    else if (wi < 31) m[t] = 0;
-    else m[t] = 91u * 8u;
-  }
-}
-__device__ __forceinline__ void dah_leaf_digest(const uint32_t (&L)[24], uint32_t (&st)[8]) {
-  uint32_t m[16];
-  sha256_init(st);
-  dah_leaf_block<0>(L, m);
-  sha256_compress(st, m);
-  dah_leaf_block<1>(L, m);
-  sha256_compress(st, m);
-}
-// RFC-6962 inner node message block B of digests Ld, Rd (8 big-endian words each): 0x01 ‖ Ld ‖ Rd ‖ pad, 65 bytes
-template <int B>
-__device__ __forceinline__ void rfc_node_block(const uint32_t* Ld, const uint32_t* Rd, uint32_t (&m)[16]) {
-  if (B == 0) {
-    m[0] = 0x01000000u | (Ld[0] >> 8);
-#pragma unroll
-    for (int t = 1; t < 8; t++) m[t] = (Ld[t - 1] << 24) | (Ld[t] >> 8);
-    m[8] = (Ld[7] << 24) | (Rd[0] >> 8);
-#pragma unroll
-    for (int t = 9; t < 16; t++) m[t] = (Rd[t - 9] << 24) | (Rd[t - 8] >> 8);
-  } else {
-    m[0] = (Rd[7] << 24) | 0x00800000u;
-#pragma unroll
-    for (int t = 1; t < 15; t++) m[t] = 0;
-    m[15] = 65u * 8u;
-  }
-}
-
 // RFC-6962 levels over the n leaf digests at sdig ([n + (n+1)/2][8] words of LDS, the first n filled), by the
-// calling workgroup (>= 128 threads); the 32-B hash goes to out.  Levels pair (2i, 2i+1) and promote an odd last
-// node, which is the same tree as HashFromByteSlices' "split at the largest power of two below n" recursion.  Once
+// calling workgroup (>= 128 threads); the 32-B hash goes to out.  Wide levels a node per thread (rfc_level_wide).  Once
 // a level has at most 64 nodes (its chain of dependent compressions is the latency), wave 0 hashes block 0 of each
 // node while wave 1 expands the node's second message block into kw (64 x kKwStride words of LDS), and the second
 // compression then runs its rounds alone.
@@ -275,24 +217,7 @@ __device__ __forceinline__ void dah_fold_kw(uint32_t* sdig, int n, uint32_t* out
   for (int cnt = n; cnt > 1;) {
     const int out_cnt = (cnt + 1) >> 1;
     if (out_cnt > 64) {
-      for (int i = threadIdx.x; i < out_cnt; i += blockDim.x) {
-        uint32_t* o = dst + i * 8;
-        const uint32_t* Ld = src + (2 * i) * 8;
-        if (2 * i + 1 >= cnt) {
-#pragma unroll
-          for (int t = 0; t < 8; t++) o[t] = Ld[t];
-          continue;
-        }
-        const uint32_t* Rd = src + (2 * i + 1) * 8;
-        uint32_t st[8], m[16];
-        sha256_init(st);
-        rfc_node_block<0>(Ld, Rd, m);
-        sha256_compress(st, m);
-        rfc_node_block<1>(Ld, Rd, m);
-        sha256_compress(st, m);
-#pragma unroll
-        for (int t = 0; t < 8; t++) o[t] = st[t];
-      }
+      rfc_level_wide(src, dst, cnt, nullptr);
     } else {
       // every lane of waves 0 and 1 computes, with full exec masks (lanes past the level's pairs hash stale,
       // in-bounds LDS words and store nothing), as in trees_lds_kernel
@@ -337,7 +262,7 @@ __global__ void __launch_bounds__(256) dah_kernel(const uint4* __restrict__ root
   const uint4* rb = roots + (size_t)blockIdx.x * n * 6;
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     uint32_t L[24], st[8];
-    load_node(rb + (size_t)i * 6, L);
+    load_rec(rb + (size_t)i * 6, L);
     dah_leaf_digest(L, st);
 #pragma unroll
     for (int t = 0; t < 8; t++) sdig[i * 8 + t] = st[t];
@@ -359,7 +284,7 @@ __global__ void __launch_bounds__(256) dah_wide_kernel(const uint4* __restrict__
   const int i = part * 256 + threadIdx.x;
   if (i < n) {
     uint32_t L[24], st[8];
-    load_node(roots + ((size_t)b * n + i) * 6, L);
+    load_rec(roots + ((size_t)b * n + i) * 6, L);
     dah_leaf_digest(L, st);
     uint4* dg = reinterpret_cast<uint4*>(digests + ((size_t)b * n + i) * 8);
     dg[0] = make_uint4(st[0], st[1], st[2], st[3]);
@@ -391,37 +316,6 @@ __global__ void __launch_bounds__(256) dah_wide_kernel(const uint4* __restrict__
 // put back to 0 for the next call) folds the block's digests into the DAH, so the step needs no DAH launch.  The
 // batched form (nmt_levels_kernel + dah_kernel) keeps every lane on a useful node and stays the throughput path.
 constexpr int kLdsRec = 7;  // uint4 per LDS record
-#ifndef CDA_TREES_TRACE
-#define CDA_TREES_TRACE 0  // diagnostic builds: per-workgroup phase timestamps of trees_lds_kernel
-#endif
-#if CDA_TREES_TRACE
-__device__ unsigned long long* g_trees_trace;  // [workgroup][32 slots][realtime, shader clock]
-#endif
-// the stamps go to LDS (thread 0) and to memory at the end, so no global store sits between the phases
-struct TreesStamps {
-  unsigned long long* v;  // LDS: [32][rt, clock]
-};
-__device__ __forceinline__ void trees_mark(TreesStamps& ts, int slot) {
-#if CDA_TREES_TRACE
-  if (threadIdx.x == 0) {
-    ts.v[2 * slot] = __builtin_amdgcn_s_memrealtime();
-    ts.v[2 * slot + 1] = __builtin_amdgcn_s_memtime();
-  }
-#else
-  (void)ts, (void)slot;
-#endif
-}
-__device__ __forceinline__ void trees_flush(const TreesStamps& ts, int lo, int hi) {
-#if CDA_TREES_TRACE
-  if (threadIdx.x == 0 && g_trees_trace)
-    for (int s = lo; s < hi; s++) {
-      g_trees_trace[((size_t)blockIdx.x * 32 + s) * 2] = ts.v[2 * s];
-      g_trees_trace[((size_t)blockIdx.x * 32 + s) * 2 + 1] = ts.v[2 * s + 1];
-    }
-#else
-  (void)ts, (void)lo, (void)hi;
-#endif
-}
 __device__ __forceinline__ void load_pair(const uint4* in, int i, uint32_t (&L)[24], uint32_t (&R)[24]) {
 #pragma unroll
   for (int q = 0; q < 6; q++) {
@@ -442,13 +336,6 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
   const bool col = tree >= (unsigned)w;
   const unsigned t = tree & (w - 1);
   const uint4* lb = leaves + (size_t)b * w * w * 6;
-#if CDA_TREES_TRACE
-  __shared__ unsigned long long tstamp[64];
-  TreesStamps tst{tstamp};
-#else
-  TreesStamps tst{nullptr};
-#endif
-  trees_mark(tst, 0);
   if (threadIdx.x == 0) last = 0;  // published by the barrier after the leaf copy
   uint4* A = lds + (size_t)half * (w + w / 2) * kLdsRec;
   uint4* B = A + (size_t)w * kLdsRec;
@@ -460,7 +347,6 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
     A[i * kLdsRec + q] = lb[rec * 6 + q];
   }
   __syncthreads();
-  trees_mark(tst, 1);
   for (int l = 1; l <= log2w; l++) {
     const uint4* in = (l & 1) ? A : B;
     uint4* out = (l & 1) ? B : A;
@@ -486,7 +372,6 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
         sha256_init(st);
         node_block<0>(L, R, m);
         sha256_compress(st, m);
-        trees_mark(tst, 2 + 3 * (l - 1));
       } else {
         uint32_t m[16];
         node_block<1>(L, R, m);
@@ -495,7 +380,6 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
         sha256_kw_store(m, kw + (64 + i) * kKwStride);
       }
       __syncthreads();
-      trees_mark(tst, 3 + 3 * (l - 1));
       if (ht < 64) {
         sha256_rounds_kw(st, kw + i * kKwStride);
         sha256_rounds_kw(st, kw + (64 + i) * kKwStride);
@@ -508,7 +392,6 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
       }
     }
     __syncthreads();
-    trees_mark(tst, 4 + 3 * (l - 1));
   }
   const uint4* root = (log2w & 1) ? B : A;
   uint4* rout = roots + ((size_t)b * n + tree) * 6;
@@ -516,11 +399,7 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
   {  // this root's DAH leaf digest: block 0 by wave 0, block 1's schedule by wave 1 meanwhile (every lane of both
      // waves computes the same digest into its own schedule row, with full exec masks; lane 0 stores it)
     uint32_t L[24], st[8], m[16];
-#pragma unroll
-    for (int q = 0; q < 6; q++) {
-      const uint4 u = root[q];
-      L[4 * q] = u.x, L[4 * q + 1] = u.y, L[4 * q + 2] = u.z, L[4 * q + 3] = u.w;
-    }
+    load_rec(root, L);
     uint32_t* kwl = kw + (ht & 63) * kKwStride;
     if (ht < 64) {
       sha256_init(st);
@@ -539,24 +418,18 @@ __global__ void __launch_bounds__(256) trees_lds_kernel(const uint4* __restrict_
     }
   }
   __syncthreads();  // both halves' roots and digests are stored (each by lanes of the wave that increments below)
-  trees_mark(tst, 26);
   if (threadIdx.x == 0 || threadIdx.x == 128) {  // one increment per tree, from the wave that stored it
     const unsigned prev = __hip_atomic_fetch_add(done + b, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     if (prev == (unsigned)n - 1) last = 1;  // at most one tree of a block is its last
   }
   __syncthreads();
-  trees_mark(tst, 27);
-  trees_flush(tst, 0, 28);
   if (!last) return;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);  // the other workgroups' digests (released before their increments)
   uint32_t* sdig = reinterpret_cast<uint32_t*>(lds);
   const uint4* src = reinterpret_cast<const uint4*>(digests + (size_t)b * n * 8);
   for (int x = threadIdx.x; x < n * 2; x += blockDim.x) reinterpret_cast<uint4*>(sdig)[x] = src[x];
   __syncthreads();
-  trees_mark(tst, 28);
   dah_fold_kw(sdig, n, dah + b * 8, sdig + (n + (n + 1) / 2) * 8);
-  trees_mark(tst, 29);
-  trees_flush(tst, 28, 30);
   if (threadIdx.x == 0) __hip_atomic_store(done + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -574,14 +447,8 @@ __global__ void __launch_bounds__(256) axis_leaf_kernel(const uint8_t* __restric
   uint32_t A[16];
   load16(sh, A);
   // Push order: leaf i+1 (if also in Q0) must not have a smaller namespace
-  if (q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n) {
-    uint32_t nb[8];
-    const uint4* p = sh + CDA_SHARE / 16;
-    uint4 v0 = p[0], v1 = p[1];
-    nb[0] = v0.x; nb[1] = v0.y; nb[2] = v0.z; nb[3] = v0.w;
-    nb[4] = v1.x; nb[5] = v1.y; nb[6] = v1.z; nb[7] = v1.w;
-    if (ns_cmp(nb, A) < 0) atomicMin(status, (unsigned long long)(i + 1));
-  }
+  if (q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n && ns_below(sh + CDA_SHARE / 16, A))
+    atomicMin(status, (unsigned long long)(i + 1));
   leaf_record(sh, A, q0, nodes + (size_t)i * 6);
 }
 
@@ -624,10 +491,8 @@ __global__ void __launch_bounds__(256) axes_leaf_kernel(const uint8_t* __restric
   load16(sh, A);
   if (q0 && i + 1 < k) {
     const size_t nxt = ax == CDA_AXIS_ROW ? cell + 1 : cell + w;
-    const uint4* p = reinterpret_cast<const uint4*>(eds + nxt * CDA_SHARE);
-    uint4 v0 = p[0], v1 = p[1];
-    uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    if (ns_cmp(nb, A) < 0) atomicMin(status + t, (unsigned long long)(i + 1));
+    if (ns_below(reinterpret_cast<const uint4*>(eds + nxt * CDA_SHARE), A))
+      atomicMin(status + t, (unsigned long long)(i + 1));
   }
   leaf_record(sh, A, q0, nodes + (size_t)gid * 6);
 }
@@ -638,8 +503,7 @@ __global__ void __launch_bounds__(256) axes_leaf_kernel(const uint8_t* __restric
 int launch_leaf_hash(const uint8_t* d_eds, void* d_leaf_nodes, unsigned long long* d_status, int k, int nblocks,
                      hipStream_t s) {
   const int w = 2 * k;
-  int log2w = 0;
-  while ((1 << log2w) < w) log2w++;
+  const int log2w = ilog2i(w);
   const uint32_t total = (uint32_t)nblocks * (uint32_t)w * (uint32_t)w;
   const uint32_t grid = (total + 255) / 256;
   hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid), dim3(256), 0, s, d_eds, (uint4*)d_leaf_nodes, d_status, k,
@@ -650,8 +514,7 @@ int launch_leaf_hash(const uint8_t* d_eds, void* d_leaf_nodes, unsigned long lon
 int launch_nmt_level(const void* d_in, void* d_out, bool from_leaves, int k, int nblocks, int level,
                      hipStream_t s) {
   const int w = 2 * k;
-  int log2w = 0;
-  while ((1 << log2w) < w) log2w++;
+  const int log2w = ilog2i(w);
   const int log2n_out = log2w - level;
   const uint32_t total = (uint32_t)nblocks * (uint32_t)(2 * w) * (1u << log2n_out);
   const uint32_t grid = (total + 255) / 256;
@@ -667,8 +530,8 @@ int launch_nmt_level(const void* d_in, void* d_out, bool from_leaves, int k, int
 int launch_trees_lds(const void* d_leaves, void* d_roots, void* d_dah, unsigned* d_done, void* d_digests, int k,
                      int nblocks, hipStream_t s) {
   const int w = 2 * k;
-  int log2w = 0;
-  while ((1 << log2w) < w) log2w++;
+  if (k < 1) return -2;
+  const int log2w = ilog2i(w);
   if ((1 << log2w) != w || log2w < 1) return -2;
   if (w > 256) return -2;  // a thread per node of level 1 within a 128-thread half
   // two trees x (w + w / 2) records of 112 B, then 2 x 2 x 64 schedule rows of kKwStride words; the DAH fold
@@ -677,18 +540,7 @@ int launch_trees_lds(const void* d_leaves, void* d_roots, void* d_dah, unsigned*
   if ((size_t)(2 * w + w) * 32 + (size_t)64 * kKwStride * 4 > lds) return -2;
   // the dynamic-LDS limit is raised to what the launch needs: 160 KiB would exceed the CU's LDS by the kernel's
   // static __shared__ word and the call would fail (and with it the launch)
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)trees_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return -1;
-#if CDA_TREES_TRACE
-  {
-    unsigned long long* tp = nullptr;
-    if (const char* e = getenv("CDA_TREES_TRACE_PTR")) tp = (unsigned long long*)(uintptr_t)strtoull(e, nullptr, 0);
-    if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_trees_trace), &tp, sizeof tp, 0, hipMemcpyHostToDevice, s) != hipSuccess)
-      return -1;
-  }
-#endif
+  if (raise_dynamic_lds((const void*)trees_lds_kernel, lds)) return -1;
   hipLaunchKernelGGL(trees_lds_kernel, dim3((unsigned)nblocks * w), dim3(256), lds, s,
                      (const uint4*)d_leaves, (uint4*)d_roots, (uint32_t*)d_dah, d_done, (uint32_t*)d_digests, log2w);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -699,11 +551,7 @@ int launch_dah_wide(const void* d_roots, void* d_dah, unsigned* d_done, void* d_
   if (n < 1 || nblocks < 1) return -2;
   const size_t lds = ((size_t)n + (n + 1) / 2) * 32 + (size_t)64 * kKwStride * 4;
   if (lds > 160 * 1024 - 64) return -2;
-  // the dynamic-LDS limit is a per-device attribute: raised on the current device for each launch that needs it
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)dah_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return -1;
+  if (raise_dynamic_lds((const void*)dah_wide_kernel, lds)) return -1;
   const int P = (n + 255) / 256;
   hipLaunchKernelGGL(dah_wide_kernel, dim3((unsigned)nblocks * P), dim3(256), lds, s, (const uint4*)d_roots,
                      (uint32_t*)d_dah, d_done, (uint32_t*)d_digests, n, P);
@@ -715,9 +563,7 @@ int launch_dah(const void* d_roots, void* d_dah, int n_roots_total, int nblocks,
   // digests, then 64 K+W schedule rows for dah_fold_kw
   const size_t lds = ((size_t)n_roots_total + (n_roots_total + 1) / 2) * 32 + (size_t)64 * kKwStride * 4;
   if (lds > 160 * 1024) return -2;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)dah_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return -1;
+  if (raise_dynamic_lds((const void*)dah_kernel, lds)) return -1;
   hipLaunchKernelGGL(dah_kernel, dim3(nblocks), dim3(256), lds, s, (const uint4*)d_roots, (uint32_t*)d_dah,
                      n_roots_total);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -734,9 +580,8 @@ int launch_axis_leaf(const uint8_t* d_leaves, int n, uint64_t square_size, uint6
 int launch_axes_roots(const uint8_t* d_eds, int k, const int* d_axes, int axis0, int ntrees, int leaf_off, int nleaves,
                       void* d_nodes, void* d_scratch, void* d_roots, unsigned long long* d_status, hipStream_t s) {
   if (ntrees <= 0) return 0;
-  int log2w = 0, log2n = 0;
-  while ((1 << log2w) < 2 * k) log2w++;
-  while ((1 << log2n) < nleaves) log2n++;
+  if (nleaves < 1) return -2;
+  const int log2w = ilog2i(2 * k), log2n = ilog2i(nleaves);
   if ((1 << log2n) != nleaves || leaf_off < 0 || leaf_off % nleaves || leaf_off + nleaves > 2 * k) return -2;
   const uint32_t total = (uint32_t)ntrees << log2n;
   hipLaunchKernelGGL(axes_leaf_kernel, dim3((total + 255) / 256), dim3(256), 0, s, d_eds, k, log2w, d_axes, axis0,
@@ -783,8 +628,7 @@ __global__ void __launch_bounds__(256) parity_compare_kernel(const uint8_t* __re
 int launch_parity_compare(const uint8_t* d_eds, int k, const int* d_axes, int naxes, const uint8_t* d_par,
                           unsigned* d_flags, hipStream_t s) {
   if (naxes <= 0) return 0;
-  int log2w = 0;
-  while ((1 << log2w) < 2 * k) log2w++;
+  const int log2w = ilog2i(2 * k);
   const size_t total = (size_t)naxes * k * (CDA_SHARE / 16);
   hipLaunchKernelGGL(parity_compare_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_eds, k, log2w,
                      d_axes, naxes, d_par, d_flags);
@@ -838,10 +682,7 @@ __global__ void __launch_bounds__(256) axes_verify_kernel(const uint8_t* __restr
     load16(sh, A);
     if (q0 && i + 1 < k) {
       const size_t nxt = ax == CDA_AXIS_ROW ? cell + 1 : cell + w;
-      const uint4* p = reinterpret_cast<const uint4*>(eds + nxt * CDA_SHARE);
-      uint4 v0 = p[0], v1 = p[1];
-      uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      if (ns_cmp(nb, A) < 0) bad = 1;
+      if (ns_below(reinterpret_cast<const uint4*>(eds + nxt * CDA_SHARE), A)) bad = 1;
     }
     leaf_record<false>(sh, A, q0, lnodes + (size_t)i * 6);
   }
@@ -849,16 +690,12 @@ __global__ void __launch_bounds__(256) axes_verify_kernel(const uint8_t* __restr
   for (int l = 1; l <= log2w; l++) {
     const int nodes = w >> l;
     if (nodes >= 64) {
-      for (int i = threadIdx.x; i < nodes; i += blockDim.x)
-        hash_node_mem(lnodes + ((size_t)(2 * i) << (l - 1)) * 6, lnodes + ((size_t)(2 * i + 1) << (l - 1)) * 6,
-                      lnodes + ((size_t)i << l) * 6);
+      lds_level_mem(lnodes, l, nodes);
     } else if (threadIdx.x < 64) {
       // a level of < 64 nodes: the whole wave computes with a full exec mask (lanes past the last node hash node 0
       // again and store nothing; reads precede the stores within the wave) -- partly masked waves ran the tree
       // kernels' small levels ~40 % slower (r04_trees_trace.log)
-      const int i = (int)threadIdx.x < nodes ? (int)threadIdx.x : 0;
-      hash_node_mem(lnodes + ((size_t)(2 * i) << (l - 1)) * 6, lnodes + ((size_t)(2 * i + 1) << (l - 1)) * 6,
-                    lnodes + ((size_t)i << l) * 6, (int)threadIdx.x < nodes);
+      lds_node_mem(lnodes, l, (int)threadIdx.x < nodes ? (int)threadIdx.x : 0, (int)threadIdx.x < nodes);
     }
     __syncthreads();
   }
@@ -878,14 +715,10 @@ __global__ void __launch_bounds__(256) axes_verify_kernel(const uint8_t* __restr
 int launch_axes_verify(const uint8_t* d_eds, int k, const int* d_axes, int ntrees, const uint8_t* d_want_rows,
                        const uint8_t* d_want_cols, unsigned* d_flag, unsigned base, bool per_tree, hipStream_t s) {
   if (ntrees <= 0) return 0;
-  int log2w = 0;
-  while ((1 << log2w) < 2 * k) log2w++;
+  const int log2w = ilog2i(2 * k);
   const size_t lds = ((size_t)2 * k) * CDA_REC_BYTES;
   if (lds > 160 * 1024) return -2;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)axes_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return -1;
+  if (raise_dynamic_lds((const void*)axes_verify_kernel, lds)) return -1;
   hipLaunchKernelGGL(axes_verify_kernel, dim3(ntrees), dim3(256), lds, s, d_eds, k, log2w, d_axes, d_want_rows,
                      d_want_cols, d_flag, base, per_tree ? 1 : 0);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -895,68 +728,6 @@ int launch_axes_verify(const uint8_t* d_eds, int k, const int* d_axes, int ntree
 constexpr int kAxisRootsKw128MaxLeaves = 512;
 // trees of at most this many leaves hash their leaves in the pipelined form (512 threads, below)
 constexpr int kAxisRootsPipeLeaves = 256;
-
-// Message block j (1..8) of a leaf: 0x00 ‖ ns ‖ share, so block j >= 1 holds share bytes 64j - 30 .. 64j + 33
-// (windows of share words 16j - 8 .. 16j + 8); block 8 ends the 542-byte message (leaf_record's blocks 1..8).
-__device__ __forceinline__ void leaf_block_words(const uint4* sh, int j, uint32_t (&m)[16]) {
-  uint32_t H[8];
-  {
-    const uint4 a = sh[4 * j - 2], b = sh[4 * j - 1];  // share words 16j - 8 .. 16j - 1
-    H[0] = a.x, H[1] = a.y, H[2] = a.z, H[3] = a.w, H[4] = b.x, H[5] = b.y, H[6] = b.z, H[7] = b.w;
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) m[i] = be_window(H[i], H[i + 1], 2);
-  if (j < 8) {
-    uint32_t C[16];
-    load16(sh + 4 * j, C);
-    m[7] = be_window(H[7], C[0], 2);
-#pragma unroll
-    for (int i = 8; i < 16; i++) m[i] = be_window(C[i - 8], C[i - 7], 2);
-  } else {
-    m[7] = be_window(H[7], 0x80u, 2);
-#pragma unroll
-    for (int i = 8; i < 15; i++) m[i] = 0;
-    m[15] = 542u * 8u;
-  }
-}
-
-// Block 0 of a leaf from its first 64 share bytes A (leaf_record's block 0; ns = share[0:29] if q0, else 0xFF x 29)
-__device__ __forceinline__ void leaf_block0_words(const uint32_t (&A)[16], bool q0, uint32_t (&m)[16]) {
-  if (q0) {
-    m[0] = be_window(0u, A[0], 3);
-#pragma unroll
-    for (int i = 1; i < 7; i++) m[i] = be_window(A[i - 1], A[i], 3);
-    m[7] = (be_window(A[6], A[7], 3) & 0xFFFF0000u) | (bswap(A[0]) >> 16);
-  } else {
-    m[0] = 0x00FFFFFFu;
-#pragma unroll
-    for (int i = 1; i < 7; i++) m[i] = 0xFFFFFFFFu;
-    m[7] = 0xFFFF0000u | (bswap(A[0]) >> 16);
-  }
-#pragma unroll
-  for (int i = 8; i < 16; i++) m[i] = be_window(A[i - 8], A[i - 7], 2);
-}
-
-// The 96-B leaf record ns ‖ ns ‖ digest ‖ 6 zero bytes from the final state (leaf_record's tail)
-__device__ __forceinline__ void leaf_record_out(const uint32_t (&A)[16], bool q0, const uint32_t (&st)[8], uint4* out) {
-  uint32_t ns[8], d[8], o[24];
-#pragma unroll
-  for (int i = 0; i < 8; i++) ns[i] = q0 ? A[i] : 0xFFFFFFFFu;
-#pragma unroll
-  for (int i = 0; i < 8; i++) d[i] = bswap(st[i]);
-#pragma unroll
-  for (int i = 0; i < 7; i++) o[i] = ns[i];
-  o[7] = (ns[7] & 0xFFu) | (ns[0] << 8);
-#pragma unroll
-  for (int i = 8; i < 14; i++) o[i] = le_window(ns[i - 8], ns[i - 7], 3);
-  o[14] = (le_window(ns[6], ns[7], 3) & 0xFFFFu) | (d[0] << 16);
-#pragma unroll
-  for (int i = 15; i < 22; i++) o[i] = le_window(d[i - 15], d[i - 14], 2);
-  o[22] = d[7] >> 16;
-  o[23] = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) out[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
-}
 
 // Roots of independent wrapper trees handed over through the per-axis seam (ErasuredNamespacedMerkleTree Push x n +
 // Root, pkg/wrapper/nmt_wrapper.go:93-124; axisq.cpp coalesces concurrent calls into one launch).  Tree t's n leaves
@@ -1000,12 +771,8 @@ __global__ void __launch_bounds__(PIPE ? 512 : 256) axis_roots_kernel(const uint
     uint32_t* const kwB = kwA + kRows;
     if (rounds) {
       load16(sh, A);
-      if (i < n && q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n) {
-        const uint4* p = sh + CDA_SHARE / 16;
-        const uint4 v0 = p[0], v1 = p[1];
-        uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        if (ns_cmp(nb, A) < 0) atomicMin(&bad, (unsigned)(i + 1));
-      }
+      if (i < n && q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n && ns_below(sh + CDA_SHARE / 16, A))
+        atomicMin(&bad, (unsigned)(i + 1));
       uint32_t m[16];
       leaf_block0_words(A, q0, m);
       sha256_init(st);
@@ -1035,12 +802,8 @@ __global__ void __launch_bounds__(PIPE ? 512 : 256) axis_roots_kernel(const uint
       const uint4* sh = reinterpret_cast<const uint4*>(base + (size_t)i * CDA_SHARE);
       uint32_t A[16];
       load16(sh, A);
-      if (q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n) {
-        const uint4* p = sh + CDA_SHARE / 16;
-        const uint4 v0 = p[0], v1 = p[1];
-        uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        if (ns_cmp(nb, A) < 0) atomicMin(&bad, (unsigned)(i + 1));
-      }
+      if (q0 && (unsigned long long)(i + 1) < square_size && i + 1 < n && ns_below(sh + CDA_SHARE / 16, A))
+        atomicMin(&bad, (unsigned)(i + 1));
       leaf_record<false>(sh, A, q0, lnodes + (size_t)i * 6);
     }
   }
@@ -1052,9 +815,7 @@ __global__ void __launch_bounds__(PIPE ? 512 : 256) axis_roots_kernel(const uint
     // round lanes of the latency path: 64 (one wave), or 128 for a level of 65..128 nodes when LDS holds the rows
     const int nr = pairs <= 64 ? 64 : 128;
     if (pairs > 128 || (nr == 128 && n > kAxisRootsKw128MaxLeaves)) {
-      for (int i = threadIdx.x; i < pairs; i += blockDim.x)
-        hash_node_mem(lnodes + ((size_t)(2 * i) << (l - 1)) * 6, lnodes + ((size_t)(2 * i + 1) << (l - 1)) * 6,
-                      lnodes + ((size_t)i << l) * 6);
+      lds_level_mem(lnodes, l, pairs);
     } else {
       // a level of <= 64 nodes is the tree's latency chain (one wave per node set, ~5.4 cycles per instruction):
       // wave 0 hashes block 0 of its node while wave 1 expands the K+W schedules of blocks 1 and 2, and after the

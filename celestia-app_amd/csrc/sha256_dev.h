@@ -64,33 +64,34 @@ __device__ __forceinline__ void sha256_init(uint32_t s[8]) {
   s[7] = 0x5be0cd19;
 }
 
-// One compression of a 16-word big-endian block (w is clobbered: used as the
-// rolling message schedule).
-__device__ __forceinline__ void sha256_compress(uint32_t s[8], uint32_t w[16]) {
-  uint32_t a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
-#pragma unroll
-  for (int t = 0; t < 64; t++) {
-    uint32_t wt;
-    if (t < 16) {
-      wt = w[t];
-    } else {
-      uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-      uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-      uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-      wt = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-      w[t & 15] = wt;
-    }
-    uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + wt;
-    uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + t2;
-  }
+// One round on the working state a..h; the additions in the order h + Σ1 + Ch + k + wt (callers that hold K + W as
+// one word pass it as k, with wt = 0).  The state is eight scalars in every compression form below, not an array or
+// a struct: from one aggregate the compiler emits the same rounds in another order (hash_node_mem's kernels 91 VGPRs
+// instead of 90).
+__device__ __forceinline__ void sha256_round(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e,
+                                             uint32_t& f, uint32_t& g, uint32_t& h, uint32_t k, uint32_t wt) {
+  const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + k + wt;
+  const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
+  h = g;
+  g = f;
+  f = e;
+  e = d + t1;
+  d = c;
+  c = b;
+  b = a;
+  a = t1 + t2;
+}
+// Message word t (a constant after unrolling) of the rolling 16-word schedule w: words 16.. expand in place.
+__device__ __forceinline__ uint32_t sha256_sched(uint32_t* w, int t) {
+  if (t < 16) return w[t];
+  const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
+  const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
+  const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
+  return w[t & 15] = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
+}
+// s += the final working state
+__device__ __forceinline__ void sha256_add(uint32_t* s, uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e,
+                                           uint32_t f, uint32_t g, uint32_t h) {
   s[0] += a;
   s[1] += b;
   s[2] += c;
@@ -99,6 +100,15 @@ __device__ __forceinline__ void sha256_compress(uint32_t s[8], uint32_t w[16]) {
   s[5] += f;
   s[6] += g;
   s[7] += h;
+}
+
+// One compression of a 16-word big-endian block (w is clobbered: used as the
+// rolling message schedule).
+__device__ __forceinline__ void sha256_compress(uint32_t s[8], uint32_t w[16]) {
+  uint32_t a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
+#pragma unroll
+  for (int t = 0; t < 64; t++) sha256_round(a, b, c, d, e, f, g, h, K256::v[t], sha256_sched(w, t));
+  sha256_add(s, a, b, c, d, e, f, g, h);
 }
 
 // Latency path (one wave per SIMD, where a lone wave issues about one instruction per 5.4 cycles whatever its
@@ -112,20 +122,7 @@ __device__ __forceinline__ void sha256_kw_store(uint32_t (&w)[16], uint32_t* kw)
   for (int t4 = 0; t4 < 16; t4++) {
     uint32_t v[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int t = 4 * t4 + j;
-      uint32_t wt;
-      if (t < 16) {
-        wt = w[t];
-      } else {
-        const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-        const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-        const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-        wt = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-        w[t & 15] = wt;
-      }
-      v[j] = wt + K256::v[t];
-    }
+    for (int j = 0; j < 4; j++) v[j] = sha256_sched(w, 4 * t4 + j) + K256::v[4 * t4 + j];
     reinterpret_cast<uint4*>(kw)[t4] = make_uint4(v[0], v[1], v[2], v[3]);
   }
 }
@@ -136,27 +133,9 @@ __device__ __forceinline__ void sha256_rounds_kw(uint32_t s[8], const uint32_t* 
     const uint4 q = reinterpret_cast<const uint4*>(kw)[t4];
     const uint32_t kv[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + kv[j];
-      const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
-      h = g;
-      g = f;
-      f = e;
-      e = d + t1;
-      d = c;
-      c = b;
-      b = a;
-      a = t1 + t2;
-    }
+    for (int j = 0; j < 4; j++) sha256_round(a, b, c, d, e, f, g, h, kv[j], 0u);
   }
-  s[0] += a;
-  s[1] += b;
-  s[2] += c;
-  s[3] += d;
-  s[4] += e;
-  s[5] += f;
-  s[6] += g;
-  s[7] += h;
+  sha256_add(s, a, b, c, d, e, f, g, h);
 }
 
 // N independent compressions advanced in lockstep (round-interleaved), giving
@@ -172,37 +151,14 @@ __device__ __forceinline__ void sha256_compress_n(uint32_t (&s)[N][8], uint32_t 
 #pragma unroll
   for (int t = 0; t < 64; t++) {
 #pragma unroll
-    for (int n = 0; n < N; n++) {
-      uint32_t wt;
-      if (t < 16) {
-        wt = w[n][t];
-      } else {
-        uint32_t w15 = w[n][(t - 15) & 15], w2 = w[n][(t - 2) & 15];
-        uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-        uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-        wt = w[n][t & 15] + s0 + w[n][(t - 7) & 15] + s1;
-        w[n][t & 15] = wt;
-      }
-      uint32_t t1 = h[n] + xor3(rotr(e[n], 6), rotr(e[n], 11), rotr(e[n], 25)) + ch(e[n], f[n], g[n]) + K256::v[t] + wt;
-      uint32_t t2 = xor3(rotr(a[n], 2), rotr(a[n], 13), rotr(a[n], 22)) + maj(a[n], b[n], c[n]);
-      h[n] = g[n];
-      g[n] = f[n];
-      f[n] = e[n];
-      e[n] = d[n] + t1;
-      d[n] = c[n];
-      c[n] = b[n];
-      b[n] = a[n];
-      a[n] = t1 + t2;
-    }
+    for (int n = 0; n < N; n++)
+      sha256_round(a[n], b[n], c[n], d[n], e[n], f[n], g[n], h[n], K256::v[t], sha256_sched(w[n], t));
     // Optional scheduling fence every SB rounds: keeps the machine scheduler
     // from hoisting message-schedule words far ahead (register pressure).
     if (SB > 0 && (t % SB) == SB - 1) __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
-  for (int n = 0; n < N; n++) {
-    s[n][0] += a[n]; s[n][1] += b[n]; s[n][2] += c[n]; s[n][3] += d[n];
-    s[n][4] += e[n]; s[n][5] += f[n]; s[n][6] += g[n]; s[n][7] += h[n];
-  }
+  for (int n = 0; n < N; n++) sha256_add(s[n], a[n], b[n], c[n], d[n], e[n], f[n], g[n], h[n]);
 }
 
 // One compression with scheduling fences every 8 rounds and after the block.
@@ -211,6 +167,9 @@ __device__ __forceinline__ void sha256_compress_n(uint32_t (&s)[N][8], uint32_t 
 // ahead.  The fences alone do not stop IR-level passes from hoisting the child
 // loads of later blocks to the top (150 VGPRs, 3 waves/SIMD); launder_after()
 // below ties each load to the previous compression: 89 VGPRs, 5 waves/SIMD.
+// It stays on sha256_compress_n<1, 8> with its copies in and out: as a plain fenced loop over the caller's state the
+// same rounds schedule differently (hash_node_mem's kernels 47 VGPRs instead of 89), which is a change to measure
+// on its own and not a rewrite.
 __device__ __forceinline__ void sha256_compress_fenced(uint32_t s[8], const uint32_t w[16]) {
   uint32_t S[1][8], W[1][16];
 #pragma unroll
@@ -232,36 +191,10 @@ __device__ __forceinline__ void sha256_compress_fenced_from(uint32_t s[8], const
   uint32_t a = mid[0], b = mid[1], c = mid[2], d = mid[3], e = mid[4], f = mid[5], g = mid[6], h = mid[7];
 #pragma unroll
   for (int t = START; t < 64; t++) {
-    uint32_t wt;
-    if (t < 16) {
-      wt = w[t];
-    } else {
-      const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-      const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-      const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-      wt = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-      w[t & 15] = wt;
-    }
-    const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + wt;
-    const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + t2;
+    sha256_round(a, b, c, d, e, f, g, h, K256::v[t], sha256_sched(w, t));
     if (FENCED && (t % 8) == 7) __builtin_amdgcn_sched_barrier(0);
   }
-  s[0] += a;
-  s[1] += b;
-  s[2] += c;
-  s[3] += d;
-  s[4] += e;
-  s[5] += f;
-  s[6] += g;
-  s[7] += h;
+  sha256_add(s, a, b, c, d, e, f, g, h);
   if (FENCED) __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -278,50 +211,11 @@ __device__ __forceinline__ void sha256_compress_skip(uint32_t s[8], const uint32
     a = mid[0], b = mid[1], c = mid[2], d = mid[3], e = mid[4], f = mid[5], g = mid[6], h = mid[7];
   } else {
 #pragma unroll
-    for (int t = 0; t < START; t++) {
-      const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + w[t];
-      const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
-      h = g;
-      g = f;
-      f = e;
-      e = d + t1;
-      d = c;
-      c = b;
-      b = a;
-      a = t1 + t2;
-    }
+    for (int t = 0; t < START; t++) sha256_round(a, b, c, d, e, f, g, h, K256::v[t], w[t]);
   }
 #pragma unroll
-  for (int t = START; t < 64; t++) {
-    uint32_t wt;
-    if (t < 16) {
-      wt = w[t];
-    } else {
-      const uint32_t w15 = w[(t - 15) & 15], w2 = w[(t - 2) & 15];
-      const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-      const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-      wt = w[t & 15] + s0 + w[(t - 7) & 15] + s1;
-      w[t & 15] = wt;
-    }
-    const uint32_t t1 = h + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + ch(e, f, g) + K256::v[t] + wt;
-    const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj(a, b, c);
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + t2;
-  }
-  s[0] += a;
-  s[1] += b;
-  s[2] += c;
-  s[3] += d;
-  s[4] += e;
-  s[5] += f;
-  s[6] += g;
-  s[7] += h;
+  for (int t = START; t < 64; t++) sha256_round(a, b, c, d, e, f, g, h, K256::v[t], sha256_sched(w, t));
+  sha256_add(s, a, b, c, d, e, f, g, h);
 }
 
 // Opaque copy of a pointer: loads through it are neither merged with earlier

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "cda_internal.h"
+#include "ctx.h"
 #include "nmt_dev.h"
 #include "sha256_dev.h"
 
@@ -32,13 +33,8 @@ __global__ void __launch_bounds__(256) region_leaf_kernel(const uint8_t* __restr
   const uint4* sh = reinterpret_cast<const uint4*>(cells + i * cell_pitch + (long long)j * CDA_SHARE);
   uint32_t A[16];
   load16(sh, A);
-  if (row_order && q0 && c + 1 < k && j + 1 < (1 << log2nc)) {
-    const uint4* p = sh + CDA_SHARE / 16;
-    const uint4 v0 = p[0], v1 = p[1];
-    const uint32_t nb[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    if (ns_cmp(nb, A) < 0)
-      atomicMin(status, ((unsigned long long)CDA_AXIS_ROW << 40) | ((unsigned long long)r << 20) | (unsigned)(c + 1));
-  }
+  if (row_order && q0 && c + 1 < k && j + 1 < (1 << log2nc) && ns_below(sh + CDA_SHARE / 16, A))
+    atomicMin(status, ((unsigned long long)CDA_AXIS_ROW << 40) | ((unsigned long long)r << 20) | (unsigned)(c + 1));
   leaf_record(sh, A, q0, recs + (i * rec_pitch + j) * 6);
 }
 
@@ -54,10 +50,9 @@ __global__ void __launch_bounds__(256) records_col_order_kernel(const uint4* __r
   if (c >= k || r + 1 >= k) return;
   const uint4* a = recs + (r * rec_pitch + j) * 6;
   const uint4* b = recs + ((r + 1) * rec_pitch + j) * 6;
-  const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
+  const uint4 a0 = a[0], a1 = a[1];
   const uint32_t na[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-  const uint32_t nb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-  if (ns_cmp(nb, na) < 0)
+  if (ns_below(b, na))
     atomicMin(status, ((unsigned long long)CDA_AXIS_COL << 40) | ((unsigned long long)c << 20) | (unsigned)(r + 1));
 }
 
@@ -102,8 +97,8 @@ __global__ void __launch_bounds__(256) tree_levels_kernel(TreeSets ts, int log2n
 // ---------------------------------------------------------------------------
 int launch_region_leaf(const uint8_t* d_cells, long long cell_pitch, int r0, int c0, int nr, int nc, int k,
                        void* d_recs, long long rec_pitch, unsigned long long* d_status, bool row_order, hipStream_t s) {
-  int log2nc = 0;
-  while ((1 << log2nc) < nc) log2nc++;
+  if (nc < 1) return -2;
+  const int log2nc = ilog2i(nc);
   if ((1 << log2nc) != nc || nr <= 0) return -2;
   const uint32_t total = (uint32_t)nr << log2nc;
   hipLaunchKernelGGL(region_leaf_kernel, dim3((total + 255) / 256), dim3(256), 0, s, d_cells, cell_pitch, r0, c0,
@@ -139,24 +134,20 @@ int launch_tree_roots(const TreeSpec* spec, int nsets, int log2n, hipStream_t s)
       d.t_stride = sp.r_stride;
       d.i_stride = 0;
     } else {
-      unsigned long long off = 0;
-      for (int q = 1; q < l; q++) off += (unsigned long long)sp.ntrees << (L - q);
-      d.p = (uint4*)sp.scratch + off * 6;
+      d.p = (uint4*)sp.scratch + levels_before(sp.ntrees, L, l) * 6;
       d.t_stride = sp.tree_fastest ? 1 : n;
       d.i_stride = sp.tree_fastest ? sp.ntrees : 1;
     }
     return d;
   };
   for (int l_in = 0; l_in < L;) {
-    int M = std::min(2, L - l_in);
-    if (L - l_in == 3) M = 3;
+    const auto [M, log2n_out] = subtree_launch(L, l_in);
     TreeSets ts{};
     for (int q = 0; q < nsets; q++) {
       for (int u = 0; u <= M; u++) ts.lv[q][u] = desc(spec[q], l_in + u);
       ts.ntrees[q] = spec[q].ntrees;
       ts.tree_fastest[q] = spec[q].tree_fastest ? 1 : 0;
     }
-    const int log2n_out = L - (l_in + M);
     const uint32_t total0 = spec[0].ntrees << log2n_out;
     const uint32_t total = total0 + (nsets > 1 ? spec[1].ntrees << log2n_out : 0);
     if (total) {

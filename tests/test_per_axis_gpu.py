@@ -128,7 +128,10 @@ def test_oversized_requests_beside_small_ones(ctx):
 
 def test_axis_root_edge_cases_match_oracle(ctx):
     """Tree shapes the wrapper allows: one leaf, odd and ragged counts, a push-order violation (the reference's error
-    with the offending leaf), and a tree wider than one workgroup's LDS (the generic level path)."""
+    with the offending leaf), and a tree wider than one workgroup's LDS (the generic level path).  Trees of 257..1024
+    leaves take the one-workgroup form without the pipelined leaves, in both of its shapes (128 round lanes up to 512
+    leaves, 64 round lanes and in-LDS node hashes above): odd and promoted nodes, a Q0 and a parity axis each, with
+    sorted namespaces so that the nodes' ranges differ."""
     import cda
     from cda import _native as N
     rng = np.random.default_rng(5)
@@ -139,12 +142,27 @@ def test_axis_root_edge_cases_match_oracle(ctx):
         rc, want, _ = O.nmt_axis_root(ss, axis, leaves)
         assert rc == 0
         assert ctx.nmt_axis_root(ss, axis, leaves) == want, (ss, n, axis)
+    for ss, n, axis in ((256, 257, 3), (256, 320, 300), (256, 512, 0), (512, 513, 7), (512, 1000, 600), (512, 1024, 1)):
+        leaves = rng.integers(0, 256, (n, 512), dtype=np.uint8)
+        leaves[:, :29] = 0
+        leaves[:, 19:29] = rng.integers(0, 256, (n, 10), dtype=np.uint8)
+        leaves = [bytes(x) for x in leaves[np.lexsort(leaves[:, :29].T[::-1])]]
+        rc, want, _ = O.nmt_axis_root(ss, axis, leaves)
+        assert rc == 0
+        assert ctx.nmt_axis_root(ss, axis, leaves) == want, (ss, n, axis)
     leaves = [bytes([0] * 28 + [9]) + bytes(483), bytes([0] * 28 + [3]) + bytes(483)] + [bytes(512)] * 6
     rc, _, el = O.nmt_axis_root(4, 0, leaves)
     assert rc == O.E_NS_ORDER and el == 1
     with pytest.raises(cda.CdaError) as ei:
         ctx.nmt_axis_root(4, 0, leaves)
     assert ei.value.code == N.E_NS_ORDER and ei.value.leaf == 1
+    # the offending leaf above 256: past the first pass of the 256-thread leaf loop
+    leaves = [bytes([0] * 28 + [3 if i == 300 else 9]) + bytes(483) for i in range(600)]
+    rc, _, el = O.nmt_axis_root(512, 2, leaves)
+    assert rc == O.E_NS_ORDER and el == 300
+    with pytest.raises(cda.CdaError) as ei:
+        ctx.nmt_axis_root(512, 2, leaves)
+    assert ei.value.code == N.E_NS_ORDER and ei.value.leaf == 300
 
 
 @pytest.mark.parametrize("k", [8, 32])
