@@ -56,6 +56,7 @@ EXPORTS = [
     "cda_multi_context", "cda_multi_device", "cda_multi_extend_commit_batch", "cda_build_ods_device",
     "cda_construct_extend_commit", "cda_multi_extend_commit_split", "cda_multi_extend_commit_split_device",
     "cda_multi_init_replicas", "cda_set_option", "cda_host_register", "cda_host_unregister",
+    "cda_square_open", "cda_square_close", "cda_square_prove", "cda_nmt_verify", "cda_nmt_verify_device",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -76,6 +77,24 @@ class ShareSegment(ctypes.Structure):
 class ShareProofInfo(ctypes.Structure):
     _fields_ = [("start_row", ctypes.c_uint32), ("end_row", ctypes.c_uint32), ("nrows", ctypes.c_uint32),
                 ("total", ctypes.c_uint32), ("naunts", ctypes.c_uint32), ("max_nodes", ctypes.c_uint32)]
+
+
+class RangeQuery(ctypes.Structure):
+    """cda_range_query: tree (axis, index).ProveRange(start, end)."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("start", ctypes.c_uint32),
+                ("end", ctypes.c_uint32)]
+
+
+class NmtProofDesc(ctypes.Structure):
+    """cda_nmt_proof_desc: one proof of a cda_nmt_verify batch."""
+    _fields_ = [("start", ctypes.c_uint32), ("end", ctypes.c_uint32), ("node_off", ctypes.c_uint32),
+                ("nnodes", ctypes.c_uint32), ("leaf_off", ctypes.c_uint32), ("root", ctypes.c_uint32)]
+
+
+# the same records as numpy rows (whole batches are built as arrays)
+RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
+NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
+                                 ("leaf_off", "<u4"), ("root", "<u4")])
 
 
 class CdaError(Exception):
@@ -148,6 +167,11 @@ def lib(path=None):
                 "cda_set_option": (I32, [P, I32, I64]),
                 "cda_host_register": (I32, [P, P, SZ]),
                 "cda_host_unregister": (I32, [P, P]),
+                "cda_square_open": (I32, [P, U32, U32, P, ctypes.POINTER(P), P, P, P, P]),
+                "cda_square_close": (None, [P]),
+                "cda_square_prove": (I32, [P, U32, P, U32, P, P, P, U64]),
+                "cda_nmt_verify": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P]),
+                "cda_nmt_verify_device": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, P]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -475,6 +499,38 @@ class Context:
         return {"start_row": info.start_row, "end_row": info.end_row, "total": info.total, "rows": rows,
                 "data_root": root.tobytes()}
 
+    # ---- sample proofs: a retained square that proves its cells, batched proof verification ----
+    def open_square(self, shares):
+        """cda_square_open: extend and commit `shares` once and keep the EDS and every tree node on the device.
+        -> Square (row_roots, col_roots, dah as attributes); use as a context manager or call close()."""
+        return Square(self, shares)
+
+    def nmt_verify(self, descs, namespaces, roots, nodes, leaves):
+        """cda_nmt_verify: nmt Proof.VerifyInclusion of a batch.  descs: NMT_PROOF_DESC_DTYPE rows; namespaces
+        (nproofs, 29); roots (nroots, 90); nodes (nnodes, 90); leaves (nleaves, 512), all uint8.  -> verdicts (nproofs,)
+        uint8, 1 = verifies."""
+        descs = np.ascontiguousarray(descs, NMT_PROOF_DESC_DTYPE)
+        n = len(descs)
+        namespaces = np.ascontiguousarray(namespaces, np.uint8).reshape(n, NAMESPACE_SIZE)
+        roots = np.ascontiguousarray(roots, np.uint8).reshape(-1, NODE_SIZE)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        leaves = np.ascontiguousarray(leaves, np.uint8).reshape(-1, SHARE_SIZE)
+        ok = np.zeros(n, np.uint8)
+        rc = self._L.cda_nmt_verify(self._h, n, _p(descs), _p(namespaces), _p(roots) if len(roots) else None,
+                                    len(roots), _p(nodes) if len(nodes) else None, len(nodes),
+                                    _p(leaves) if len(leaves) else None, len(leaves), _p(ok))
+        _check(rc, ctx=self)
+        return ok
+
+    def nmt_verify_device(self, nproofs, d_descs, d_namespaces, d_roots, nroots, d_nodes, nnodes, d_leaves, nleaves,
+                          d_ok, stream=None):
+        """cda_nmt_verify_device: the same with device addresses, asynchronous on `stream`."""
+        rc = self._L.cda_nmt_verify_device(self._h, nproofs, ctypes.c_void_p(d_descs), ctypes.c_void_p(d_namespaces),
+                                           ctypes.c_void_p(d_roots), nroots, ctypes.c_void_p(d_nodes), nnodes,
+                                           ctypes.c_void_p(d_leaves), nleaves, ctypes.c_void_p(d_ok),
+                                           ctypes.c_void_p(stream or 0))
+        _check(rc, ctx=self)
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -492,6 +548,70 @@ class Context:
         for i in range(n):
             out[parts[i].decode()] = (float(ms[i]), int(cnt[i]))
         return out
+
+
+class Square:
+    """cda_square: one extended block retained on the device (Context.open_square)."""
+
+    def __init__(self, ctx, shares):
+        shares = np.ascontiguousarray(shares, np.uint8)
+        count, L = shares.shape
+        self.k = max(1, int(round(count ** 0.5)))
+        w = 2 * self.k
+        self.row_roots = np.empty((w, NODE_SIZE), np.uint8)
+        self.col_roots = np.empty((w, NODE_SIZE), np.uint8)
+        dah = np.empty(32, np.uint8)
+        self._ctx, self._h = ctx, None
+        h = ctypes.c_void_p()
+        err = ErrInfo()
+        rc = ctx._L.cda_square_open(ctx._h, count, L, _p(shares), ctypes.byref(h), _p(self.row_roots),
+                                    _p(self.col_roots), _p(dah), ctypes.byref(err))
+        _check(rc, err, ctx)
+        self._h = h
+        self.dah = dah.tobytes()
+        self.max_nodes = 2 * (w.bit_length() - 1)
+
+    def prove(self, queries, want_shares=True):
+        """cda_square_prove.  queries: (axis, index, start, end) tuples or RANGE_QUERY_DTYPE rows.
+        -> (counts (nq,) int32, nodes (nq, max_nodes, 90) uint8, shares (sum(end - start), 512) uint8 or None): query
+        q's proof is nodes[q, :counts[q]], its cells follow those of the queries before it."""
+        q = queries if isinstance(queries, np.ndarray) and queries.dtype == RANGE_QUERY_DTYPE else \
+            np.array([tuple(x) for x in queries], RANGE_QUERY_DTYPE)
+        q = np.ascontiguousarray(q)
+        nq = len(q)
+        mn = max(1, self.max_nodes)
+        counts = np.zeros(nq, np.int32)
+        nodes = np.zeros((nq, mn, NODE_SIZE), np.uint8)
+        ncells = int((q["end"].astype(np.int64) - q["start"].astype(np.int64)).clip(min=0).sum())
+        shares = np.zeros((ncells, SHARE_SIZE), np.uint8) if want_shares else None
+        rc = self._ctx._L.cda_square_prove(self._h, nq, _p(q), mn, _p(counts), _p(nodes), _p(shares),
+                                           shares.nbytes if want_shares else 0)
+        _check(rc, ctx=self._ctx)
+        return counts, nodes, shares
+
+    def prove_device(self, queries, max_nodes, d_counts, d_nodes, d_shares=0, shares_cap=0):
+        """cda_square_prove with the outputs at device addresses (queries stay host records)."""
+        q = np.ascontiguousarray(queries, RANGE_QUERY_DTYPE)
+        rc = self._ctx._L.cda_square_prove(self._h, len(q), _p(q), max_nodes, ctypes.c_void_p(d_counts),
+                                           ctypes.c_void_p(d_nodes), ctypes.c_void_p(d_shares or None), shares_cap)
+        _check(rc, ctx=self._ctx)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._ctx._L.cda_square_close(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default = None

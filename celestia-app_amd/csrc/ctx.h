@@ -16,6 +16,7 @@ struct AxisQueue;  // axisq.cpp
 struct Stager;     // staging.cpp
 struct Consensus;  // consensus.cpp
 }
+struct cda_square;  // sampling.cpp
 
 struct cda_ctx {
   int device = 0;
@@ -56,6 +57,8 @@ struct cda_ctx {
   Buf ods, eds, leaf, scratch, roots, dah, status, plan, payload;
   Buf done;  // per-block tree counters of the small-batch tree launch (trees_lds_kernel), kept at zero
   Buf nodes;  // node export (inclusion.cpp): the exported trees' per-tree node lists, packed on the device
+  // the open retained squares (sampling.cpp): each owns its device memory; cda_free releases it and detaches them
+  std::vector<cda_square*> squares;
   // one square split over devices (split.cpp): this device's slab, row / column slabs, leaf records, send blocks,
   // tree scratch, per-device results (meta) and, on the first device, the gathered results
   Buf sp_ods, sp_R, sp_LR, sp_S, sp_C, sp_LC, sp_scratch, sp_meta, sp_gather;
@@ -112,6 +115,9 @@ void flush_profile(cda_ctx* c);
 int ilog2i(uint32_t v);
 bool is_pow2(uint64_t v);
 void set_err(cda_err_info* e, int code, int axis, int index, int leaf, int block);
+// Square-shape checks of da.ExtendShares / rsmt2d for the entry points that keep or export tree nodes (inclusion.cpp)
+int square_k(uint32_t count, uint32_t share_len, uint32_t* k, cda_err_info* err);
+void release_squares(cda_ctx* c);  // sampling.cpp: cda_free's part for the open squares (lock held)
 // 96-B records -> packed 90-B nodes
 void pack_roots(const uint8_t* recs, uint32_t n, uint8_t* out);
 // device status word -> CDA_OK / CDA_E_NS_ORDER (+ err detail)

@@ -22,9 +22,7 @@
 
 using namespace cda;
 
-namespace {
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+namespace cda {
 
 // Square-shape checks of da.ExtendShares / rsmt2d for the node-export entry points.
 int square_k(uint32_t count, uint32_t share_len, uint32_t* k, cda_err_info* err) {
@@ -36,6 +34,12 @@ int square_k(uint32_t count, uint32_t share_len, uint32_t* k, cda_err_info* err)
   *k = kk;
   return CDA_OK;
 }
+
+}  // namespace cda
+
+namespace {
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // node (h, p) of a perfect tree of w leaves exported as levels (leaves first, root last), 90 B per node
 const uint8_t* tree_node(const uint8_t* base, uint32_t w, int h, uint32_t p) {

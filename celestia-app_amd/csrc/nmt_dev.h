@@ -70,14 +70,23 @@ constexpr uint32_t kParityLeafMid7[8] = {0x1ca5c518, 0x33e5c969, 0xbd2d00ce, 0xa
 #define CDA_NO_PARITY_MID 0  // diagnostic A/B: every leaf and inner node through all 64 rounds of its first block
 #endif
 
-// Block 0 from the first 64 share bytes A: 0x00 ‖ ns[0..29) ‖ share[0..34)
-__device__ __forceinline__ void leaf_block0_words(const uint32_t (&A)[16], bool q0, uint32_t (&m)[16]) {
-  if (q0) {
-    m[0] = be_window(0u, A[0], 3);
+// Words 0..7 of block 0, 0x00 ‖ ns[0..29) ‖ share[0..2), for the namespace in the eight little-endian words NS (29
+// bytes: the upper three bytes of NS[7] are not read) and the share's first word a0
+__device__ __forceinline__ void leaf_block0_ns_words(const uint32_t* NS, uint32_t a0, uint32_t (&m)[16]) {
+  m[0] = be_window(0u, NS[0], 3);
 #pragma unroll
-    for (int i = 1; i < 7; i++) m[i] = be_window(A[i - 1], A[i], 3);
-    // bytes 28..31 = ns[27], ns[28], share[0], share[1]
-    m[7] = (be_window(A[6], A[7], 3) & 0xFFFF0000u) | (bswap(A[0]) >> 16);
+  for (int i = 1; i < 7; i++) m[i] = be_window(NS[i - 1], NS[i], 3);
+  // bytes 28..31 = ns[27], ns[28], share[0], share[1]
+  m[7] = (be_window(NS[6], NS[7], 3) & 0xFFFF0000u) | (bswap(a0) >> 16);
+}
+// Block 0 from the first 64 share bytes A: 0x00 ‖ ns[0..29) ‖ share[0..34), ns = share[0:29] if q0 else 0xFF x 29;
+// with NS (a compile-time choice of the caller), the namespace supplied there instead
+__device__ __forceinline__ void leaf_block0_words(const uint32_t (&A)[16], bool q0, uint32_t (&m)[16],
+                                                  const uint32_t* NS = nullptr) {
+  if (NS) {
+    leaf_block0_ns_words(NS, A[0], m);
+  } else if (q0) {
+    leaf_block0_ns_words(A, A[0], m);
   } else {
     m[0] = 0x00FFFFFFu;
 #pragma unroll
@@ -129,17 +138,22 @@ __device__ __forceinline__ void rec_digest_words(uint32_t w14, const uint32_t* s
   o[23] = 0;
 }
 
-// The leaf record from the final state
-__device__ __forceinline__ void leaf_record_out(const uint32_t (&A)[16], bool q0, const uint32_t (&st)[8], uint4* out) {
-  uint32_t ns[8], o[24];
-#pragma unroll
-  for (int i = 0; i < 8; i++) ns[i] = q0 ? A[i] : 0xFFFFFFFFu;
+// The leaf record ns ‖ ns ‖ digest from the namespace words (as leaf_block0_ns_words takes them) and the final state
+__device__ __forceinline__ void leaf_record_words(const uint32_t (&ns)[8], const uint32_t (&st)[8],
+                                                  uint32_t (&o)[24]) {
 #pragma unroll
   for (int i = 0; i < 7; i++) o[i] = ns[i];
   o[7] = (ns[7] & 0xFFu) | (ns[0] << 8);
 #pragma unroll
   for (int i = 8; i < 14; i++) o[i] = le_window(ns[i - 8], ns[i - 7], 3);
   rec_digest_words(le_window(ns[6], ns[7], 3), st, o);
+}
+// The leaf record from the final state
+__device__ __forceinline__ void leaf_record_out(const uint32_t (&A)[16], bool q0, const uint32_t (&st)[8], uint4* out) {
+  uint32_t ns[8], o[24];
+#pragma unroll
+  for (int i = 0; i < 8; i++) ns[i] = q0 ? A[i] : 0xFFFFFFFFu;
+  leaf_record_words(ns, st, o);
   store_rec(out, o);
 }
 
@@ -150,19 +164,23 @@ __device__ __forceinline__ void leaf_record_out(const uint32_t (&A)[16], bool q0
 // block): loaded a compression apart, the line's second half missed in L2 often enough that the leaf kernel fetched
 // 1.31x its bytes (all 128-B requests, profiles/r04_rdreq_sizes.json).  PAIRS = false: one chunk per block (16
 // fewer VGPRs; repair's root check, whose kernel would otherwise pass 128).
+// leaf_digest_state is the hashing alone (st = the final state); with NS (a compile-time choice of the caller) the
+// leaf's namespace is the one supplied there instead of a derived one: nmt Proof.VerifyInclusion's leaf (q0 is then not
+// read, and NS is read for block 0 only: the caller builds the record with leaf_record_words).
 template <bool PAIRS = true>
-__device__ __forceinline__ void leaf_record(const uint4* sh, const uint32_t (&A)[16], bool q0, uint4* out) {
+__device__ __forceinline__ void leaf_digest_state(const uint4* sh, const uint32_t (&A)[16], bool q0,
+                                                  const uint32_t* NS, uint32_t (&st)[8]) {
   uint32_t N[16];
   if (PAIRS) load16(sh + 4, N);  // chunk 1, the rest of the line A came from
-  uint32_t st[8], m[16];
+  uint32_t m[16];
   sha256_init(st);
-  leaf_block0_words(A, q0, m);
+  leaf_block0_words(A, q0, m, NS);
   // wave-uniform only (a wave of parity and Q0 cells runs all 64 rounds), and one copy of rounds 7..63 for both
   // cases: in a wave of parity cells m[0..6] already hold the constant words the schedule reads
   uint32_t mid[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) mid[i] = kParityLeafMid7[i];
-  sha256_compress_skip<7>(st, mid, m, !CDA_NO_PARITY_MID && __all(!q0));
+  sha256_compress_skip<7>(st, mid, m, !NS && !CDA_NO_PARITY_MID && __all(!q0));
   uint32_t H[8];  // the upper half of the previous 16-word chunk
 #pragma unroll
   for (int i = 0; i < 8; i++) H[i] = A[8 + i];
@@ -185,6 +203,11 @@ __device__ __forceinline__ void leaf_record(const uint4* sh, const uint32_t (&A)
   }
   leaf_block_words(H, nullptr, true, m);
   sha256_compress(st, m);
+}
+template <bool PAIRS = true>
+__device__ __forceinline__ void leaf_record(const uint4* sh, const uint32_t (&A)[16], bool q0, uint4* out) {
+  uint32_t st[8];
+  leaf_digest_state<PAIRS>(sh, A, q0, nullptr, st);
   leaf_record_out(A, q0, st, out);
 }
 

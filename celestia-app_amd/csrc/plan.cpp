@@ -1,6 +1,8 @@
 // plan.cpp — host-only planners (plan.h).  No HIP: built into libcda and, alone, under the CPU sanitizers.
 #include "plan.h"
 
+#include "nmt_verify_rule.h"
+
 #include <string.h>
 
 #include <algorithm>
@@ -205,6 +207,23 @@ void prove_rec(int h, uint32_t p, uint32_t s, uint32_t e, std::vector<std::pair<
 
 void prove_range(int L, uint32_t s, uint32_t e, std::vector<std::pair<int, uint32_t>>& out) {
   prove_rec(L, 0, s, e, out);
+}
+
+bool verify_walk(uint32_t s, uint32_t e, uint32_t nnodes, std::vector<VerifyStep>& steps, uint32_t* tail) {
+  steps.clear();
+  VerifyWalk w;
+  if (s >= e || !w.init(s, e, nnodes)) return false;
+  for (int l = 0; l < w.levels; l++) {
+    VerifyStep st;
+    st.level = l;
+    w.step(st.left, st.right);
+    st.lo = w.lo;
+    st.hi = w.hi;
+    steps.push_back(st);
+    w.up();
+  }
+  *tail = w.rp;
+  return true;
 }
 
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len) {

@@ -6,6 +6,8 @@
 //   sparse_shares_needed,    go-square shares.SparseSharesNeeded, inclusion.SubTreeWidth and
 //   subtree_width, mountains MerkleMountainRangeSizes (inclusion.cpp, cda_blob_commitments)
 //   prove_range              nmt buildRangeProof on a perfect tree (inclusion.cpp, cda_share_inclusion_proof)
+//   verify_walk              nmt Proof.VerifyInclusion's node schedule (nmt_verify_rule.h: what the kernels of
+//                            cda_nmt_verify evaluate per proof)
 //   check_square_plan        the share-layout plan of cda_build_ods_device (square.cpp)
 #pragma once
 #include <stddef.h>
@@ -94,6 +96,16 @@ uint32_t round_down_pow2(uint32_t v);
 // nmt buildRangeProof on a perfect tree of 2^L leaves: the maximal subtrees outside [s, e), left to right, as
 // (height, position) pairs.
 void prove_range(int L, uint32_t s, uint32_t e, std::vector<std::pair<int, uint32_t>>& out);
+
+// nmt Proof.VerifyInclusion of leaves [s, e) with nnodes proof nodes as a schedule (nmt_verify_rule.h): one step per
+// level below the root of the subtree of 2 * splitpoint(e) leaves, then `tail` = the first node applied above it.
+// False: fewer nodes than the left hull needs (the proof is rejected).
+struct VerifyStep {
+  int level;
+  uint32_t lo, hi;  // the level's span with both extensions
+  int left, right;  // the node in front of / behind the span, -1: none (an odd last node goes up unchanged)
+};
+bool verify_walk(uint32_t s, uint32_t e, uint32_t nnodes, std::vector<VerifyStep>& steps, uint32_t* tail);
 
 // shares a sequence of `len` bytes needs (compact: 474 / 478 per share; sparse: 478 / 482; padding: 1)
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len);

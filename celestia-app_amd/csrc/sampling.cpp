@@ -1,0 +1,287 @@
+// sampling.cpp — C ABI of the sample proofs (include/cda.h): a retained square that proves any of its cells, and
+// batched nmt.Proof.VerifyInclusion.
+//
+//   cda_square_open / close    da.ExtendShares + NewDataAvailabilityHeader once; the EDS and every node of the 4k
+//                              trees stay in device memory of the handle
+//   cda_square_prove           wrapper ErasuredNamespacedMerkleTree.ProveRange (pkg/wrapper/nmt_wrapper.go:127-130) of
+//                              any row or column tree, many ranges per launch
+//   cda_nmt_verify[_device]    nmt Proof.VerifyInclusion as ShareProof.VerifyProof calls it
+//                              (pkg/proof/share_proof.go:53-82), many proofs per launch
+// The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.
+//
+// Ownership: a square's device memory is one allocation of its own, so no other call on the context can touch it.
+// The context lists its open squares; cda_free releases their device memory and detaches them (ctx = null), after
+// which a handle is good for cda_square_close alone, which then only frees the host struct.  As for every other
+// call, cda_free must not run concurrently with calls on the context or its squares.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+#include "nmt_verify_rule.h"
+#include "sampling.h"
+
+using namespace cda;
+
+struct cda_square {
+  cda_ctx* c = nullptr;  // null once the context was freed
+  uint32_t k = 0;
+  void* mem = nullptr;  // eds | leaf records | level records (SquareView)
+  SquareView view{};
+};
+
+namespace {
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+void release_square_memory(cda_square* sq) {
+  if (sq->mem) (void)hipFree(sq->mem);
+  sq->mem = nullptr;
+}
+
+// copy to or from caller memory that may be host or device memory
+bool copy_any(cda_ctx* c, void* dst, const void* src, size_t n, hipStream_t s) {
+  return n == 0 || dev_ok(c, hipMemcpyAsync(dst, src, n, hipMemcpyDefault, s), "copy");
+}
+
+}  // namespace
+
+namespace cda {
+
+void release_squares(cda_ctx* c) {
+  for (cda_square* sq : c->squares) {
+    release_square_memory(sq);
+    sq->c = nullptr;
+  }
+  c->squares.clear();
+}
+
+}  // namespace cda
+
+extern "C" {
+
+int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_t* shares, cda_square** out,
+                    uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
+  CDA_API_TRY
+  set_err(err, CDA_OK, -1, -1, -1, -1);
+  if (out) *out = nullptr;
+  if (!c || !shares || !out || !row_roots || !col_roots || !dah) return CDA_E_ARG;
+  uint32_t k = 0;
+  if (int rc = square_k(count, share_len, &k, err)) return rc;
+  Lock l(c);
+  const uint32_t w = 2 * k;
+  const int L = ilog2i(w);
+  const size_t cells = (size_t)w * w, ods_b = (size_t)k * k * CDA_SHARE, eds_b = cells * CDA_SHARE;
+  const size_t leaf_b = cells * CDA_REC_BYTES, levels_b = square_level_offset(L, L + 1) * CDA_REC_BYTES;
+  // the ODS is uploaded into the level records' place: the extension has read it before level 1 is written
+  const size_t tail_b = align256(std::max(levels_b, ods_b)), meta_b = 512;  // meta: status [0, 8) | dah [256, 288)
+  struct Owner {  // releases a half-built square on every failure path (including an exception)
+    cda_square* sq;
+    ~Owner() {
+      if (!sq) return;
+      release_square_memory(sq);
+      delete sq;
+    }
+  } own{new cda_square()};
+  cda_square* sq = own.sq;
+  fault_point("alloc");
+  if (!dev_ok(c, hipMalloc(&sq->mem, eds_b + align256(leaf_b) + tail_b + meta_b), "hipMalloc")) return CDA_E_DEVICE;
+  uint8_t* d_eds = (uint8_t*)sq->mem;
+  uint8_t* d_leaf = d_eds + eds_b;
+  uint8_t* d_levels = d_leaf + align256(leaf_b);
+  uint8_t* meta = d_levels + tail_b;
+  unsigned long long* d_status = (unsigned long long*)meta;
+  uint8_t* d_dah = meta + 256;
+  auto level = [&](int h) { return d_levels + square_level_offset(L, h) * CDA_REC_BYTES; };
+  hipStream_t s = c->stream;
+  int rc;
+  if (!dev_ok(c, hipMemcpyAsync(d_levels, shares, ods_b, hipMemcpyHostToDevice, s), "H2D") ||
+      !dev_ok(c, hipMemsetAsync(d_status, 0xFF, 8, s), "memset"))
+    return CDA_E_DEVICE;
+  if ((rc = enqueue_rs(c, k, 1, d_levels, d_eds, s))) return rc;
+  {
+    ProfScope ps(c, "leaf_hash", s);
+    if (launch_leaf_hash(d_eds, d_leaf, d_status, (int)k, 1, s)) return CDA_E_DEVICE;
+  }
+  // the per-level path of the node export (inclusion.cpp), every level's records in a place of their own
+  for (int h = 1; h <= L; h++) {
+    ProfScope ps(c, h == 1 ? "nmt_level1" : "nmt_level", s);
+    if (launch_nmt_level(h == 1 ? d_leaf : level(h - 1), level(h), h == 1, (int)k, 1, h, s)) return CDA_E_DEVICE;
+  }
+  uint8_t* d_roots = level(L);  // 2w root records, rows then columns
+  {
+    ProfScope ps(c, "dah", s);
+    const int lr = launch_dah(d_roots, d_dah, (int)(2 * w), 1, s);
+    if (lr) return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;
+  }
+  const size_t roots_b = (size_t)2 * w * CDA_REC_BYTES;
+  std::vector<uint8_t> recs(roots_b);
+  uint64_t st = 0;
+  if (!dev_ok(c, hipMemcpyAsync(recs.data(), d_roots, roots_b, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipMemcpyAsync(dah, d_dah, 32, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipMemcpyAsync(&st, d_status, 8, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  pack_roots(recs.data(), w, row_roots);
+  pack_roots(recs.data() + (size_t)w * CDA_REC_BYTES, w, col_roots);
+  if ((rc = map_status(st, 0, err))) return rc;
+  sq->c = c;
+  sq->k = k;
+  sq->view = SquareView{d_eds, d_leaf, d_levels, L};
+  c->squares.push_back(sq);
+  own.sq = nullptr;
+  *out = sq;
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+void cda_square_close(cda_square* sq) {
+  if (!sq) return;
+  try {
+    if (cda_ctx* c = sq->c) {
+      Lock l(c);
+      (void)hipStreamSynchronize(c->stream);
+      c->squares.erase(std::remove(c->squares.begin(), c->squares.end(), sq), c->squares.end());
+      release_square_memory(sq);
+    }
+  } catch (...) {  // nothing may escape the C ABI
+  }
+  delete sq;
+}
+
+int cda_square_prove(cda_square* sq, uint32_t nq, const cda_range_query* q, uint32_t max_nodes, int32_t* counts,
+                     uint8_t* nodes, uint8_t* shares_or_null, uint64_t shares_cap) {
+  cda_ctx* c = sq ? sq->c : nullptr;
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;  // null, or a square whose context was freed
+  if (nq == 0) return CDA_OK;
+  if (!q || !counts || !nodes) return CDA_E_ARG;
+  if (nq > (1u << 24)) return CDA_E_UNSUPPORTED;
+  const uint32_t w = 2 * sq->k;
+  if (max_nodes < 2 * (uint32_t)sq->view.log2w) return CDA_E_ARG;
+  uint64_t ncells = 0;
+  for (uint32_t i = 0; i < nq; i++) {
+    if (q[i].axis > 1 || q[i].index >= w || q[i].start >= q[i].end || q[i].end > w) return CDA_E_ARG;
+    ncells += q[i].end - q[i].start;
+  }
+  if (shares_or_null && ncells * CDA_SHARE > shares_cap) return CDA_E_ARG;
+  if (ncells > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;
+  Lock l(c);
+  hipStream_t s = c->stream;
+  // staging in the context's workspace: queries | counts | share offsets, the nodes, the cells
+  const size_t q_b = align256((size_t)nq * sizeof(cda_range_query)), cnt_b = align256((size_t)nq * 4);
+  const size_t nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE, shares_b = shares_or_null ? ncells * CDA_SHARE : 0;
+  int rc;
+  if ((rc = ensure(c, c->plan, q_b + 2 * cnt_b)) || (rc = ensure(c, c->nodes, nodes_b)) ||
+      (shares_b && (rc = ensure(c, c->payload, shares_b))))
+    return rc;
+  cda_range_query* d_q = (cda_range_query*)c->plan.p;
+  int32_t* d_counts = (int32_t*)((uint8_t*)c->plan.p + q_b);
+  uint32_t* d_off = (uint32_t*)((uint8_t*)c->plan.p + q_b + cnt_b);
+  uint8_t* d_shares = shares_b ? (uint8_t*)c->payload.p : nullptr;
+  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_range_query), hipMemcpyHostToDevice, s), "H2D"))
+    return CDA_E_DEVICE;
+  {
+    ProfScope ps(c, "square_prove", s);
+    if (launch_square_prove(sq->view, d_q, nq, max_nodes, d_counts, (uint8_t*)c->nodes.p, d_shares ? d_off : nullptr,
+                            d_shares, s))
+      return CDA_E_DEVICE;
+  }
+  if (!copy_any(c, counts, d_counts, (size_t)nq * 4, s) || !copy_any(c, nodes, c->nodes.p, nodes_b, s) ||
+      !copy_any(c, shares_or_null, d_shares, shares_b, s) || !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_nmt_verify(cda_ctx* c, uint32_t nproofs, const cda_nmt_proof_desc* descs, const uint8_t* namespaces,
+                   const uint8_t* roots, uint32_t nroots, const uint8_t* nodes, uint32_t nnodes_total,
+                   const uint8_t* leaves, uint32_t nleaves_total, uint8_t* ok) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!descs || !namespaces || !ok || (nroots && !roots) || (nnodes_total && !nodes) || (nleaves_total && !leaves))
+    return CDA_E_ARG;
+  bool ranges = false;
+  for (uint32_t i = 0; i < nproofs; i++) {
+    if (descs[i].end > kVerifyMaxEnd) return CDA_E_ARG;
+    ranges = ranges || (descs[i].start < descs[i].end && descs[i].end - descs[i].start > 1);
+  }
+  Lock l(c);
+  hipStream_t s = c->stream;
+  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_nmt_proof_desc));
+  const size_t ns_b = align256((size_t)nproofs * CDA_NAMESPACE_SIZE), ok_b = align256(nproofs);
+  const size_t roots_b = (size_t)nroots * CDA_NODE_SIZE, nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE;
+  const size_t leaves_b = (size_t)nleaves_total * CDA_SHARE;
+  int rc;
+  if ((rc = ensure(c, c->plan, desc_b + ns_b + ok_b + align256(roots_b))) || (rc = ensure(c, c->nodes, nodes_b)) ||
+      (rc = ensure(c, c->payload, leaves_b)))
+    return rc;
+  uint8_t* base = (uint8_t*)c->plan.p;
+  VerifyArgs a{};
+  a.descs = (const cda_nmt_proof_desc*)base;
+  a.namespaces = base + desc_b;
+  a.ok = base + desc_b + ns_b;
+  a.roots = base + desc_b + ns_b + ok_b;
+  a.nodes = (const uint8_t*)c->nodes.p;
+  a.leaves = (const uint8_t*)c->payload.p;
+  a.nproofs = nproofs;
+  a.nroots = nroots;
+  a.nnodes_total = nnodes_total;
+  a.nleaves_total = nleaves_total;
+  if (!dev_ok(c, hipMemcpyAsync(base, descs, (size_t)nproofs * sizeof(cda_nmt_proof_desc), hipMemcpyHostToDevice, s),
+              "H2D") ||
+      !dev_ok(c, hipMemcpyAsync(base + desc_b, namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE,
+                                hipMemcpyHostToDevice, s), "H2D") ||
+      (roots_b && !dev_ok(c, hipMemcpyAsync(base + desc_b + ns_b + ok_b, roots, roots_b, hipMemcpyHostToDevice, s),
+                          "H2D")))
+    return CDA_E_DEVICE;
+  if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
+  if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
+  {
+    ProfScope ps(c, "nmt_verify", s);
+    if (launch_nmt_verify(a, ranges, s)) return CDA_E_DEVICE;
+  }
+  if (!dev_ok(c, hipMemcpyAsync(ok, a.ok, nproofs, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_nmt_verify_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
+                          const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
+                          const void* d_leaves, uint32_t nleaves_total, void* d_ok, void* stream) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!d_descs || !d_namespaces || !d_ok || (nroots && !d_roots) || (nnodes_total && !d_nodes) ||
+      (nleaves_total && !d_leaves))
+    return CDA_E_ARG;
+  // the kernels read shares 16 bytes and nodes, roots and descriptors 4 bytes at a time
+  if (((uintptr_t)d_leaves & 15) || (((uintptr_t)d_nodes | (uintptr_t)d_roots | (uintptr_t)d_descs) & 3))
+    return CDA_E_ARG;
+  VerifyArgs a{};
+  a.descs = (const cda_nmt_proof_desc*)d_descs;
+  a.namespaces = (const uint8_t*)d_namespaces;
+  a.roots = (const uint8_t*)d_roots;
+  a.nodes = (const uint8_t*)d_nodes;
+  a.leaves = (const uint8_t*)d_leaves;
+  a.ok = (uint8_t*)d_ok;
+  a.nproofs = nproofs;
+  a.nroots = nroots;
+  a.nnodes_total = nnodes_total;
+  a.nleaves_total = nleaves_total;
+  DevLock dl(c, (hipStream_t)stream);
+  ProfScope ps(c, "nmt_verify", dl.s);
+  // the descriptors are device memory: whether any proof has more than one leaf is not known here
+  return launch_nmt_verify(a, true, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+}  // extern "C"

@@ -299,6 +299,52 @@ int cda_share_inclusion_proof(cda_ctx* ctx, uint32_t count, uint32_t share_len, 
                               uint8_t* aunts, int32_t* nmt_start, int32_t* nmt_end, int32_t* nmt_count,
                               uint8_t* nmt_nodes, uint8_t* data_root, cda_err_info* err);
 
+/* ---- sample proofs: prove any EDS cell, verify proved cells in batches ---- */
+/* A retained square: the block is extended once and the EDS with every node of its 4k trees stays in
+ * device memory that belongs to the handle (never the context's workspace: other calls on the context
+ * leave it untouched).  Calls on a handle take its context's lock.  cda_free of a context with open
+ * squares releases their device memory; such a handle stays valid for cda_square_close only (every
+ * other call on it returns CDA_E_ARG), so close after free never touches the device. */
+typedef struct cda_square cda_square;
+/* da.ExtendShares + NewDataAvailabilityHeader as cda_extend_commit (same outputs, same
+ * CDA_E_NS_ORDER mapping, on which no handle is returned); *out receives the handle. */
+int cda_square_open(cda_ctx* ctx, uint32_t count, uint32_t share_len, const uint8_t* shares, cda_square** out,
+                    uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah, cda_err_info* err);
+void cda_square_close(cda_square* sq);
+
+typedef struct {
+  uint32_t axis, index; /* CDA_AXIS_ROW / CDA_AXIS_COL, 0 <= index < 2k: the tree */
+  uint32_t start, end;  /* wrapper ErasuredNamespacedMerkleTree.ProveRange(start, end), 0 <= start < end <= 2k */
+} cda_range_query;
+/* nq range proofs in one launch (wrapper.ProveRange, pkg/wrapper/nmt_wrapper.go:127-130, of any row or
+ * column tree, parity cells included).  counts[q] = proof nodes of query q; nodes: nq x max_nodes slots
+ * of 90 B, a query's nodes left to right in its first counts[q] slots (the others zero);
+ * max_nodes >= 2 log2(2k), else CDA_E_ARG.  shares_or_null receives the proved cells packed in query
+ * order, sum(end - start) x 512 B; shares_cap is its size in bytes (CDA_E_ARG if too small).  A query
+ * outside the square gives CDA_E_ARG before anything is launched.  q is host memory; counts, nodes and
+ * shares_or_null may each be host or device memory. */
+int cda_square_prove(cda_square* sq, uint32_t nq, const cda_range_query* q, uint32_t max_nodes, int32_t* counts,
+                     uint8_t* nodes, uint8_t* shares_or_null, uint64_t shares_cap);
+
+/* Batched nmt.Proof.VerifyInclusion (IgnoreMaxNamespace, as ShareProof.VerifyProof calls it).  Proof p:
+ * namespace = namespaces[29p, 29p + 29), leaves = leaves[leaf_off, leaf_off + end - start) (512-B shares
+ * without the namespace prefix: a leaf hashes as ns ‖ ns ‖ SHA256(0x00 ‖ ns ‖ share) with the supplied
+ * namespace), nodes = nodes[node_off, node_off + nnodes) of 90 B, root = roots[root] of 90 B. */
+typedef struct {
+  uint32_t start, end, node_off, nnodes, leaf_off, root;
+} cda_nmt_proof_desc;
+/* ok[p] = 1 if proof p verifies, else 0: a false proof is a verdict, never an error code.  A descriptor
+ * that points outside the totals or has start >= end gets 0 and is not read through.  CDA_E_ARG if a
+ * descriptor has end > 65536 (the widest axis the codec accepts). */
+int cda_nmt_verify(cda_ctx* ctx, uint32_t nproofs, const cda_nmt_proof_desc* descs, const uint8_t* namespaces,
+                   const uint8_t* roots, uint32_t nroots, const uint8_t* nodes, uint32_t nnodes_total,
+                   const uint8_t* leaves, uint32_t nleaves_total, uint8_t* ok);
+/* The same with every pointer in device memory (d_leaves 16-byte, d_nodes / d_roots / d_descs 4-byte
+ * aligned, else CDA_E_ARG), asynchronous on `stream`; a descriptor with end > 65536 gets ok = 0. */
+int cda_nmt_verify_device(cda_ctx* ctx, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
+                          const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
+                          const void* d_leaves, uint32_t nleaves_total, void* d_ok, void* stream);
+
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
  * host plans the layout -- which sequence or blob goes where, the PFB share indexes, the compact
