@@ -57,6 +57,7 @@ EXPORTS = [
     "cda_construct_extend_commit", "cda_multi_extend_commit_split", "cda_multi_extend_commit_split_device",
     "cda_multi_init_replicas", "cda_set_option", "cda_host_register", "cda_host_unregister",
     "cda_square_open", "cda_square_close", "cda_square_prove", "cda_nmt_verify", "cda_nmt_verify_device",
+    "cda_square_share_proofs", "cda_share_proofs_validate", "cda_share_proofs_validate_device",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -91,7 +92,40 @@ class NmtProofDesc(ctypes.Structure):
                 ("nnodes", ctypes.c_uint32), ("leaf_off", ctypes.c_uint32), ("root", ctypes.c_uint32)]
 
 
+class ShareRange(ctypes.Structure):
+    """cda_share_range: ODS shares [start, end), row-major."""
+    _fields_ = [("start", ctypes.c_uint32), ("end", ctypes.c_uint32)]
+
+
+class ShareRow(ctypes.Structure):
+    """cda_share_row: one row of a ShareProof (its NMTProof and the merkle Proof of its row root)."""
+    _fields_ = [("nmt_start", ctypes.c_int32), ("nmt_end", ctypes.c_int32), ("node_off", ctypes.c_uint32),
+                ("nnodes", ctypes.c_uint32), ("total", ctypes.c_int64), ("index", ctypes.c_int64),
+                ("aunt_off", ctypes.c_uint32), ("naunts", ctypes.c_uint32), ("row", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32)]
+
+
+class ShareProofDesc(ctypes.Structure):
+    """cda_share_proof_desc: one ShareProof of a cda_share_proofs_validate batch."""
+    _fields_ = [("row_off", ctypes.c_uint32), ("nshare_proofs", ctypes.c_uint32), ("nrow_roots", ctypes.c_uint32),
+                ("nrow_proofs", ctypes.c_uint32), ("leaf_off", ctypes.c_uint32), ("nleaves", ctypes.c_uint32),
+                ("start_row", ctypes.c_uint32), ("end_row", ctypes.c_uint32), ("data_root", ctypes.c_uint32),
+                ("ns", ctypes.c_uint8 * 29), ("pad_", ctypes.c_uint8 * 3)]
+
+
+# ShareProof.Validate's checks in its order (include/cda.h CDA_SP_*)
+SP_VALID, SP_PROOF_COUNT, SP_DATA_COUNT, SP_NEG_START, SP_EMPTY_RANGE, SP_ROW_COUNT, SP_ROW_PROOFS, SP_ROW_PROOF, \
+    SP_SHARE_PROOF, SP_MALFORMED = range(10)
+
 # the same records as numpy rows (whole batches are built as arrays)
+SHARE_RANGE_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4")])
+SHARE_ROW_DTYPE = np.dtype([("nmt_start", "<i4"), ("nmt_end", "<i4"), ("node_off", "<u4"), ("nnodes", "<u4"),
+                            ("total", "<i8"), ("index", "<i8"), ("aunt_off", "<u4"), ("naunts", "<u4"),
+                            ("row", "<u4"), ("pad_", "<u4")])
+SHARE_PROOF_DESC_DTYPE = np.dtype([("row_off", "<u4"), ("nshare_proofs", "<u4"), ("nrow_roots", "<u4"),
+                                   ("nrow_proofs", "<u4"), ("leaf_off", "<u4"), ("nleaves", "<u4"),
+                                   ("start_row", "<u4"), ("end_row", "<u4"), ("data_root", "<u4"),
+                                   ("ns", "u1", (29,)), ("pad_", "u1", (3,))])
 RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
 NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("leaf_off", "<u4"), ("root", "<u4")])
@@ -172,6 +206,10 @@ def lib(path=None):
                 "cda_square_prove": (I32, [P, U32, P, U32, P, P, P, U64]),
                 "cda_nmt_verify": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P]),
                 "cda_nmt_verify_device": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, P]),
+                "cda_square_share_proofs": (I32, [P, U32, P, U32, U32, P, P, P, P, P, P, P, U64, P]),
+                "cda_share_proofs_validate": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32, P]),
+                "cda_share_proofs_validate_device": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32, P,
+                                                             P]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -531,6 +569,39 @@ class Context:
                                            ctypes.c_void_p(stream or 0))
         _check(rc, ctx=self)
 
+    def share_proofs_validate(self, descs, rows, row_roots, leaf_hashes, nodes, aunts, leaves, data_roots):
+        """cda_share_proofs_validate: ShareProof.Validate of a batch.  descs: SHARE_PROOF_DESC_DTYPE rows; rows:
+        SHARE_ROW_DTYPE rows with row_roots (nrows, 90) and leaf_hashes (nrows, 32); nodes (n, 90); aunts (n, 32);
+        leaves (n, 512); data_roots (n, 32), all uint8.  -> verdicts (nproofs,) int32, SP_* codes."""
+        descs = np.ascontiguousarray(descs, SHARE_PROOF_DESC_DTYPE)
+        rows = np.ascontiguousarray(rows, SHARE_ROW_DTYPE)
+        nrows = len(rows)
+        row_roots = np.ascontiguousarray(row_roots, np.uint8).reshape(nrows, NODE_SIZE)
+        leaf_hashes = np.ascontiguousarray(leaf_hashes, np.uint8).reshape(nrows, 32)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        aunts = np.ascontiguousarray(aunts, np.uint8).reshape(-1, 32)
+        leaves = np.ascontiguousarray(leaves, np.uint8).reshape(-1, SHARE_SIZE)
+        data_roots = np.ascontiguousarray(data_roots, np.uint8).reshape(-1, 32)
+        verdicts = np.full(len(descs), -1, np.int32)
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_share_proofs_validate(self._h, len(descs), p(descs), p(rows), p(row_roots), p(leaf_hashes),
+                                               nrows, p(nodes), len(nodes), p(aunts), len(aunts), p(leaves),
+                                               len(leaves), p(data_roots), len(data_roots), _p(verdicts))
+        _check(rc, ctx=self)
+        return verdicts
+
+    def share_proofs_validate_device(self, nproofs, d_descs, d_rows, d_row_roots, d_leaf_hashes, nrows, d_nodes, nnodes,
+                                     d_aunts, naunts, d_leaves, nleaves, d_data_roots, nroots, d_verdicts, stream=None):
+        """cda_share_proofs_validate_device: the same with device addresses, asynchronous on `stream`."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_share_proofs_validate_device(self._h, nproofs, V(d_descs), V(d_rows), V(d_row_roots),
+                                                      V(d_leaf_hashes), nrows, V(d_nodes), nnodes, V(d_aunts), naunts,
+                                                      V(d_leaves), nleaves, V(d_data_roots), nroots, V(d_verdicts),
+                                                      V(stream or 0))
+        _check(rc, ctx=self)
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -595,6 +666,69 @@ class Square:
         rc = self._ctx._L.cda_square_prove(self._h, len(q), _p(q), max_nodes, ctypes.c_void_p(d_counts),
                                            ctypes.c_void_p(d_nodes), ctypes.c_void_p(d_shares or None), shares_cap)
         _check(rc, ctx=self._ctx)
+
+    @staticmethod
+    def share_proof_sizes(k, ranges):
+        """(row records, shares) the proofs of `ranges` ((start, end) ODS share ranges) of a k x k square take."""
+        nrows = sum((int(e) - 1) // k - int(s) // k + 1 for s, e in ranges)
+        return nrows, sum(int(e) - int(s) for s, e in ranges)
+
+    def share_proofs_raw(self, ranges, want_shares=True):
+        """cda_square_share_proofs: pkg/proof NewShareInclusionProof of every (start, end) ODS share range, one
+        launch.  -> dict of the flat arrays the call writes: row_off (nq + 1,), rows (SHARE_ROW_DTYPE), nodes
+        (nrows, max_nodes, 90), row_roots (nrows, 90), leaf_hashes (nrows, 32), aunts (nrows, log2(4k), 32), shares
+        (n, 512) or None, data_root bytes.  Query q's records are rows[row_off[q]:row_off[q + 1]]."""
+        q = np.array([(int(s), int(e)) for s, e in ranges], SHARE_RANGE_DTYPE).reshape(-1)
+        nq, mn, na = len(q), max(1, self.max_nodes), (4 * self.k).bit_length() - 1
+        # sized on the host from ranges that may be bad: the library checks them (clip keeps the sizes sane)
+        nrows, nshares = self.share_proof_sizes(self.k, [(s, max(s + 1, min(e, self.k * self.k))) for s, e in
+                                                         ((int(x["start"]), int(x["end"])) for x in q)])
+        out = {"row_off": np.zeros(nq + 1, np.uint32), "rows": np.zeros(nrows, SHARE_ROW_DTYPE),
+               "nodes": np.zeros((nrows, mn, NODE_SIZE), np.uint8), "row_roots": np.zeros((nrows, NODE_SIZE), np.uint8),
+               "leaf_hashes": np.zeros((nrows, 32), np.uint8), "aunts": np.zeros((nrows, na, 32), np.uint8),
+               "shares": np.zeros((nshares, SHARE_SIZE), np.uint8) if want_shares else None}
+        root = np.zeros(32, np.uint8)
+        rc = self._ctx._L.cda_square_share_proofs(self._h, nq, _p(q), mn, nrows, _p(out["row_off"]), _p(out["rows"]),
+                                                  _p(out["nodes"]), _p(out["row_roots"]), _p(out["leaf_hashes"]),
+                                                  _p(out["aunts"]), _p(out["shares"]) if want_shares else None,
+                                                  out["shares"].nbytes if want_shares else 0, _p(root))
+        _check(rc, ctx=self._ctx)
+        out["data_root"] = root.tobytes()
+        return out
+
+    def share_proofs_device(self, ranges, max_nodes, rows_cap, d_row_off, d_rows, d_nodes, d_row_roots, d_leaf_hashes,
+                            d_aunts, d_shares, shares_cap, d_data_root):
+        """cda_square_share_proofs with the outputs at device addresses (the ranges stay host records)."""
+        q = np.array([(int(s), int(e)) for s, e in ranges], SHARE_RANGE_DTYPE).reshape(-1)
+        V = ctypes.c_void_p
+        rc = self._ctx._L.cda_square_share_proofs(self._h, len(q), _p(q), max_nodes, rows_cap, V(d_row_off), V(d_rows),
+                                                  V(d_nodes), V(d_row_roots), V(d_leaf_hashes), V(d_aunts),
+                                                  V(d_shares or None), shares_cap, V(d_data_root))
+        _check(rc, ctx=self._ctx)
+
+    def share_proofs(self, ranges, namespaces=None):
+        """pkg/proof NewShareInclusionProof for every (start, end) ODS share range, one launch -> list of
+        cda.proof.ShareProof.  namespaces: the 29-byte namespace of each range (ParseNamespace's result); default:
+        the namespace of the range's first share."""
+        from . import proof as P
+        ranges = [(int(s), int(e)) for s, e in ranges]
+        raw = self.share_proofs_raw(ranges)
+        rows, out, cursor = raw["rows"], [], 0
+        for i, (s, e) in enumerate(ranges):
+            lo, hi = int(raw["row_off"][i]), int(raw["row_off"][i + 1])
+            data = [raw["shares"][cursor + j].tobytes() for j in range(e - s)]
+            cursor += e - s
+            ns = bytes(namespaces[i]) if namespaces is not None else data[0][:NAMESPACE_SIZE]
+            nmt = [P.NMTProof(int(rows[r]["nmt_start"]), int(rows[r]["nmt_end"]),
+                              [raw["nodes"][r, j].tobytes() for j in range(int(rows[r]["nnodes"]))])
+                   for r in range(lo, hi)]
+            row_proof = P.RowProof([raw["row_roots"][r].tobytes() for r in range(lo, hi)],
+                                   [P.Proof(int(rows[r]["total"]), int(rows[r]["index"]),
+                                            raw["leaf_hashes"][r].tobytes(),
+                                            [raw["aunts"][r, j].tobytes() for j in range(int(rows[r]["naunts"]))])
+                                    for r in range(lo, hi)], int(rows[lo]["row"]), int(rows[hi - 1]["row"]))
+            out.append(P.ShareProof(data, nmt, ns[1:], row_proof, ns[0], raw["data_root"]))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

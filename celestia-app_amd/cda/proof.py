@@ -227,8 +227,11 @@ def parse_namespace(raw_shares, start_share, end_share):
     return ns
 
 
-def new_share_inclusion_proof(data_square, namespace, start, end, ctx=None):
-    """NewShareInclusionProof(dataSquare, namespace, shares.NewRange(start, end))."""
+def new_share_inclusion_proof(data_square, namespace, start, end, ctx=None, square=None):
+    """NewShareInclusionProof(dataSquare, namespace, shares.NewRange(start, end)).  square: an open Square of the same
+    data square (Context.open_square): the proof is gathered from its retained nodes, nothing is extended again."""
+    if square is not None:
+        return square.share_proofs([(start, end)], [bytes(namespace)])[0]
     ctx = ctx or N.default_context()
     arr = np.stack([np.frombuffer(bytes(s), np.uint8) for s in data_square])
     out = ctx.share_inclusion_proof(arr, start, end)
@@ -244,3 +247,114 @@ def new_share_inclusion_proof(data_square, namespace, start, end, ctx=None):
         share_proofs.append(NMTProof(r["start"], r["end"], r["nodes"]))
     namespace = bytes(namespace)
     return ShareProof(data, share_proofs, namespace[1:], row_proof, namespace[0], out["data_root"])
+
+
+def new_tx_inclusion_proof(txs, tx_index, square=None, ctx=None, **construct_args):
+    """NewTxInclusionProof(txs, txIndex, appVersion) (pkg/proof/proof.go:18-50): the share proof of the shares that
+    hold tx `tx_index` of the block `txs`: its namespace is PAY_FOR_BLOB when the tx is a BlobTx, else TRANSACTION.
+    square: an open Square of the block's data square (see new_share_inclusion_proof)."""
+    from . import square as S
+    if tx_index < 0 or tx_index >= len(txs):
+        raise ProofError(f"txIndex {tx_index} out of bounds")
+    start, end = S.find_tx_share_range(txs, tx_index, **construct_args)
+    namespace = S.PAY_FOR_BLOB_NAMESPACE if S.unmarshal_blob_tx(txs[tx_index]) is not None else S.TX_NAMESPACE
+    _, data_square, _ = S.construct(txs, **construct_args)
+    return new_share_inclusion_proof(data_square, namespace, start, end, ctx=ctx, square=square)
+
+
+# ---- batched ShareProof.Validate on the device (cda_share_proofs_validate) ----
+def verdict_error(verdict, proof):
+    """The ProofError ShareProof.validate raises at the check verdict `verdict` (CDA_SP_*) names; None for 0."""
+    rp = proof.row_proof
+    if verdict == N.SP_VALID:
+        return None
+    if verdict == N.SP_PROOF_COUNT:
+        return ProofError(f"the number of share proofs {len(proof.share_proofs)} must equal the number of row "
+                          f"roots {len(rp.row_roots)}")
+    if verdict == N.SP_DATA_COUNT:
+        in_proofs = sum(p.end - p.start for p in proof.share_proofs)
+        return ProofError(f"the number of shares {len(proof.data)} must equal the number of shares in share "
+                          f"proofs {in_proofs}")
+    if verdict == N.SP_NEG_START:
+        return ProofError("proof index cannot be negative")
+    if verdict == N.SP_EMPTY_RANGE:
+        return ProofError("proof total must be positive")
+    if verdict == N.SP_ROW_COUNT:
+        return ProofError(f"the number of rows {rp.end_row - rp.start_row + 1} must equal the number of row "
+                          f"roots {len(rp.row_roots)}")
+    if verdict == N.SP_ROW_PROOFS:
+        return ProofError(f"the number of proofs {len(rp.proofs)} must equal the number of row roots "
+                          f"{len(rp.row_roots)}")
+    if verdict == N.SP_ROW_PROOF:
+        return ProofError("row proof failed to verify")
+    if verdict == N.SP_SHARE_PROOF:
+        return ProofError("share proof failed to verify")
+    return ProofError("malformed share proof descriptor")
+
+
+def pack_share_proofs(proofs, root_index):
+    """The flat arrays cda_share_proofs_validate takes for `proofs` (ShareProof list; proof i validates against data
+    root root_index[i]) -> dict(descs, rows, row_roots, leaf_hashes, nodes, aunts, leaves).  Row record j of a proof
+    holds share_proofs[j], row_roots[j] and proofs[j] where each exists (a well-formed proof has as many of each).
+    Sizes the C records cannot hold (a namespace that is not 29 bytes, nodes that are not 90, shares that are not 512,
+    hashes that are not 32) raise ValueError."""
+    NODE, SHARE = N.NODE_SIZE, N.SHARE_SIZE
+    nrec = [max(len(p.share_proofs), len(p.row_proof.row_roots), len(p.row_proof.proofs)) for p in proofs]
+    descs = np.zeros(len(proofs), N.SHARE_PROOF_DESC_DTYPE)
+    rows = np.zeros(sum(nrec), N.SHARE_ROW_DTYPE)
+    row_roots = np.zeros((len(rows), NODE), np.uint8)
+    leaf_hashes = np.zeros((len(rows), 32), np.uint8)
+    nodes, aunts, leaves = [], [], []
+
+    def sized(x, n, what):
+        x = bytes(x)
+        if len(x) != n:
+            raise ValueError(f"{what} of {len(x)} bytes: cda_share_proofs_validate takes {n}")
+        return x
+    r = 0
+    for i, p in enumerate(proofs):
+        rp = p.row_proof
+        ns = sized(bytes([p.namespace_version]) + bytes(p.namespace_id), appconsts.NAMESPACE_SIZE, "namespace")
+        descs[i] = (r, len(p.share_proofs), len(rp.row_roots), len(rp.proofs), len(leaves), len(p.data),
+                    rp.start_row, rp.end_row, root_index[i], np.frombuffer(ns, np.uint8), 0)
+        leaves += [sized(x, SHARE, "share") for x in p.data]
+        for j in range(nrec[i]):
+            rec = rows[r + j]
+            if j < len(p.share_proofs):
+                sp = p.share_proofs[j]
+                rec["nmt_start"], rec["nmt_end"], rec["node_off"], rec["nnodes"] = sp.start, sp.end, len(nodes), \
+                    len(sp.nodes)
+                nodes += [sized(x, NODE, "node") for x in sp.nodes]
+            if j < len(rp.row_roots):
+                row_roots[r + j] = np.frombuffer(sized(rp.row_roots[j], NODE, "row root"), np.uint8)
+            if j < len(rp.proofs):
+                mp = rp.proofs[j]
+                rec["total"], rec["index"], rec["aunt_off"], rec["naunts"] = mp.total, mp.index, len(aunts), \
+                    len(mp.aunts)
+                leaf_hashes[r + j] = np.frombuffer(sized(mp.leaf_hash, 32, "leaf hash"), np.uint8)
+                aunts += [sized(x, 32, "aunt") for x in mp.aunts]
+        r += nrec[i]
+
+    def flat(items, n):
+        return np.frombuffer(b"".join(items), np.uint8).reshape(-1, n) if items else np.zeros((0, n), np.uint8)
+    return {"descs": descs, "rows": rows, "row_roots": row_roots, "leaf_hashes": leaf_hashes,
+            "nodes": flat(nodes, NODE), "aunts": flat(aunts, 32), "leaves": flat(leaves, SHARE)}
+
+
+def validate_share_proofs(ctx, proofs, data_roots):
+    """ShareProof.validate of every proof on the device, one call (cda_share_proofs_validate).  data_roots: one root
+    for all proofs (bytes) or one per proof.  -> per proof None, or the ProofError ShareProof.validate(root) raises."""
+    proofs = list(proofs)
+    if not proofs:
+        return []
+    roots = [bytes(data_roots)] * len(proofs) if isinstance(data_roots, (bytes, bytearray)) else \
+        [bytes(x) for x in data_roots]
+    if len(roots) != len(proofs) or any(len(x) != 32 for x in roots):
+        raise ValueError("one 32-byte data root, or one per proof")
+    uniq = {}
+    index = [uniq.setdefault(x, len(uniq)) for x in roots]
+    a = pack_share_proofs(proofs, index)
+    verdicts = ctx.share_proofs_validate(a["descs"], a["rows"], a["row_roots"], a["leaf_hashes"], a["nodes"],
+                                         a["aunts"], a["leaves"],
+                                         np.frombuffer(b"".join(uniq), np.uint8).reshape(-1, 32))
+    return [verdict_error(int(v), p) for v, p in zip(verdicts, proofs)]

@@ -294,6 +294,39 @@ def construct(txs, max_square_size=appconsts.DEFAULT_SQUARE_SIZE_UPPER_BOUND,
     return ss, render(segs), info
 
 
+def tx_share_ranges(txs, max_square_size=appconsts.DEFAULT_SQUARE_SIZE_UPPER_BOUND,
+                    subtree_root_threshold=appconsts.SUBTREE_ROOT_THRESHOLD, square_size_upper_bound=None):
+    """find_tx_share_range of every tx of the block from one layout -> list of (start, end)."""
+    _, segs, _ = plan(txs, max_square_size, subtree_root_threshold, square_size_upper_bound)
+
+    def share_of(byte):
+        if byte < FIRST_COMPACT_SHARE_CONTENT_SIZE:
+            return 0
+        return 1 + (byte - FIRST_COMPACT_SHARE_CONTENT_SIZE) // CONTINUATION_COMPACT_SHARE_CONTENT_SIZE
+    ranges = {}
+    for ns in (TX_NAMESPACE, PAY_FOR_BLOB_NAMESPACE):
+        seg = next((sg for sg in segs if sg["kind"] == "compact" and sg["ns"] == ns), None)
+        out, lo = [], 0
+        for u in seg["payload"] if seg else []:
+            hi = lo + len(varint(len(u))) + len(u)
+            out.append((seg["first"] + share_of(lo), seg["first"] + share_of(hi - 1) + 1))
+            lo = hi
+        ranges[ns] = iter(out)
+    # a tx's place in its own sequence is its place among the txs of its kind
+    return [next(ranges[PAY_FOR_BLOB_NAMESPACE if unmarshal_blob_tx(t) is not None else TX_NAMESPACE]) for t in txs]
+
+
+def find_tx_share_range(txs, tx_index, max_square_size=appconsts.DEFAULT_SQUARE_SIZE_UPPER_BOUND,
+                        subtree_root_threshold=appconsts.SUBTREE_ROOT_THRESHOLD, square_size_upper_bound=None):
+    """square.TxShareRange (go-square Builder.FindTxShareRange, as pkg/proof/proof.go:28 calls it) -> (start, end):
+    the shares of the square of `txs` that hold tx `tx_index`: those of its compact sequence that its length prefix
+    and its bytes fall into.  A BlobTx is found as its index wrapper in the PAY_FOR_BLOB sequence, which starts after
+    the TRANSACTION shares."""
+    if tx_index < 0 or tx_index >= len(txs):
+        raise SquareError(f"txIndex {tx_index} out of bounds")
+    return tx_share_ranges(txs, max_square_size, subtree_root_threshold, square_size_upper_bound)[tx_index]
+
+
 SEG_KIND = {"compact": 0, "sparse": 1, "padding": 2}  # CDA_SEG_* (include/cda.h)
 
 

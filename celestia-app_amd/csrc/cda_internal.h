@@ -80,6 +80,9 @@ int launch_nmt_level(const void* d_in, void* d_out, bool from_leaves, int k, int
 int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k, int nblocks, hipStream_t s,
                      void* prof_ctx);
 int launch_dah(const void* d_roots, void* d_dah, int n_roots_total, int nblocks, hipStream_t s);
+// launch_dah of one block that also writes the whole RFC-6962 tree (2n - 1 digests of 32 B, leaf hashes first, the
+// root last) to d_nodes_out
+int launch_dah_tree(const void* d_roots, void* d_dah, void* d_nodes_out, int n_roots_total, hipStream_t s);
 // the batched path's DAH: digests by ceil(n / 256) workgroups per block, fold by the last (counters in d_done)
 int launch_dah_wide(const void* d_roots, void* d_dah, unsigned* d_done, void* d_digests, int n, int nblocks,
                     hipStream_t s);

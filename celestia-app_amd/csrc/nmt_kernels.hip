@@ -210,10 +210,15 @@ int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k,
 // calling workgroup (>= 128 threads); the 32-B hash goes to out.  Wide levels a node per thread (rfc_level_wide).  Once
 // a level has at most 64 nodes (its chain of dependent compressions is the latency), wave 0 hashes block 0 of each
 // node while wave 1 expands the node's second message block into kw (64 x kKwStride words of LDS), and the second
-// compression then runs its rounds alone.
-__device__ __forceinline__ void dah_fold_kw(uint32_t* sdig, int n, uint32_t* out, uint32_t* kw) {
+// compression then runs its rounds alone.  NODES: every level's digests also go to nodes_out as bytes, level by level
+// after the n leaf digests the caller wrote there (the tree cda_extend_commit_nodes exports as dah_nodes); without
+// it the code is what it was.
+template <bool NODES = false>
+__device__ __forceinline__ void dah_fold_kw(uint32_t* sdig, int n, uint32_t* out, uint32_t* kw,
+                                            uint32_t* nodes_out = nullptr) {
   uint32_t* src = sdig;
   uint32_t* dst = sdig + n * 8;
+  size_t base = (size_t)n;  // NODES: nodes of the levels below the one being written
   for (int cnt = n; cnt > 1;) {
     const int out_cnt = (cnt + 1) >> 1;
     if (out_cnt > 64) {
@@ -247,6 +252,10 @@ __device__ __forceinline__ void dah_fold_kw(uint32_t* sdig, int n, uint32_t* out
       }
     }
     __syncthreads();
+    if (NODES) {
+      for (int i = threadIdx.x; i < out_cnt * 8; i += blockDim.x) nodes_out[base * 8 + i] = bswap(dst[i]);
+      base += out_cnt;
+    }
     uint32_t* tmp = src;
     src = dst;
     dst = tmp;
@@ -269,6 +278,26 @@ __global__ void __launch_bounds__(256) dah_kernel(const uint4* __restrict__ root
   }
   __syncthreads();
   dah_fold_kw(sdig, n, dah + blockIdx.x * 8, sdig + (n + (n + 1) / 2) * 8);
+}
+
+// dah_kernel of one block that also leaves the whole tree in nodes_out (2n - 1 digests of 32 B for a power-of-two n:
+// the leaf hashes, then each level, the data root last): a retained square's data-root tree (cda_square_open), from
+// the same launch that gives its DAH.
+__global__ void __launch_bounds__(256) dah_tree_kernel(const uint4* __restrict__ roots, uint32_t* __restrict__ dah,
+                                                       uint32_t* __restrict__ nodes_out, int n) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t sdig[];  // as dah_kernel
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    uint32_t L[24], st[8];
+    load_rec(roots + (size_t)i * 6, L);
+    dah_leaf_digest(L, st);
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+      sdig[i * 8 + t] = st[t];
+      nodes_out[(size_t)i * 8 + t] = bswap(st[t]);
+    }
+  }
+  __syncthreads();
+  dah_fold_kw<true>(sdig, n, dah, sdig + (n + (n + 1) / 2) * 8, nodes_out);
 }
 
 // DAH of a batch, wide form: the root digests by P = ceil(n / 256) workgroups per block, one root per thread, and
@@ -566,6 +595,16 @@ int launch_dah(const void* d_roots, void* d_dah, int n_roots_total, int nblocks,
   if (raise_dynamic_lds((const void*)dah_kernel, lds)) return -1;
   hipLaunchKernelGGL(dah_kernel, dim3(nblocks), dim3(256), lds, s, (const uint4*)d_roots, (uint32_t*)d_dah,
                      n_roots_total);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_dah_tree(const void* d_roots, void* d_dah, void* d_nodes_out, int n_roots_total, hipStream_t s) {
+  if (n_roots_total < 1) return -2;
+  const size_t lds = ((size_t)n_roots_total + (n_roots_total + 1) / 2) * 32 + (size_t)64 * kKwStride * 4;  // launch_dah's
+  if (lds > 160 * 1024) return -2;
+  if (raise_dynamic_lds((const void*)dah_tree_kernel, lds)) return -1;
+  hipLaunchKernelGGL(dah_tree_kernel, dim3(1), dim3(256), lds, s, (const uint4*)d_roots, (uint32_t*)d_dah,
+                     (uint32_t*)d_nodes_out, n_roots_total);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

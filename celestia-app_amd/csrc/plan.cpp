@@ -1,6 +1,7 @@
 // plan.cpp — host-only planners (plan.h).  No HIP: built into libcda and, alone, under the CPU sanitizers.
 #include "plan.h"
 
+#include "merkle_walk_rule.h"
 #include "nmt_verify_rule.h"
 
 #include <string.h>
@@ -223,6 +224,14 @@ bool verify_walk(uint32_t s, uint32_t e, uint32_t nnodes, std::vector<VerifyStep
     w.up();
   }
   *tail = w.rp;
+  return true;
+}
+
+bool merkle_walk(int64_t total, int64_t index, uint64_t naunts, std::vector<uint8_t>& aunt_on_left) {
+  aunt_on_left.clear();
+  MerkleWalk w;
+  if (!w.init(total, index, naunts)) return false;
+  for (int j = 0; j < w.depth; j++) aunt_on_left.push_back(w.aunt_on_left(j) ? 1 : 0);
   return true;
 }
 

@@ -107,6 +107,10 @@ struct VerifyStep {
 };
 bool verify_walk(uint32_t s, uint32_t e, uint32_t nnodes, std::vector<VerifyStep>& steps, uint32_t* tail);
 
+// go-square merkle Proof.Verify's path for (total, index) with naunts aunts (merkle_walk_rule.h): aunt_on_left[j] says
+// on which side aunt j is hashed, bottom-up.  False: the proof is rejected by its numbers alone.
+bool merkle_walk(int64_t total, int64_t index, uint64_t naunts, std::vector<uint8_t>& aunt_on_left);
+
 // shares a sequence of `len` bytes needs (compact: 474 / 478 per share; sparse: 478 / 482; padding: 1)
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len);
 // cda_build_ods_device's plan check: the segments tile [0, k*k) in order, every payload lies inside `data`

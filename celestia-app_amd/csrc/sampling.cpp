@@ -7,6 +7,9 @@
 //                              any row or column tree, many ranges per launch
 //   cda_nmt_verify[_device]    nmt Proof.VerifyInclusion as ShareProof.VerifyProof calls it
 //                              (pkg/proof/share_proof.go:53-82), many proofs per launch
+//   cda_square_share_proofs    pkg/proof NewShareInclusionProof (proof.go:55-167) for many share ranges per launch:
+//                              NMT range proofs, row roots and their RFC-6962 proofs in the data root
+//   cda_share_proofs_validate[_device]  ShareProof.Validate (share_proof.go:16-82, row_proof.go:13-48) of a batch
 // The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.
 //
 // Ownership: a square's device memory is one allocation of its own, so no other call on the context can touch it.
@@ -28,7 +31,7 @@ using namespace cda;
 struct cda_square {
   cda_ctx* c = nullptr;  // null once the context was freed
   uint32_t k = 0;
-  void* mem = nullptr;  // eds | leaf records | level records (SquareView)
+  void* mem = nullptr;  // eds | leaf records | level records | data-root tree (SquareView)
   SquareView view{};
 };
 
@@ -76,7 +79,8 @@ int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_
   const size_t cells = (size_t)w * w, ods_b = (size_t)k * k * CDA_SHARE, eds_b = cells * CDA_SHARE;
   const size_t leaf_b = cells * CDA_REC_BYTES, levels_b = square_level_offset(L, L + 1) * CDA_REC_BYTES;
   // the ODS is uploaded into the level records' place: the extension has read it before level 1 is written
-  const size_t tail_b = align256(std::max(levels_b, ods_b)), meta_b = 512;  // meta: status [0, 8) | dah [256, 288)
+  // meta: status [0, 8) | dah [256, 288) | data-root tree [512, ..)
+  const size_t tail_b = align256(std::max(levels_b, ods_b)), dn = 2 * (size_t)(2 * w) - 1, meta_b = 512 + dn * 32;
   struct Owner {  // releases a half-built square on every failure path (including an exception)
     cda_square* sq;
     ~Owner() {
@@ -94,6 +98,7 @@ int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_
   uint8_t* meta = d_levels + tail_b;
   unsigned long long* d_status = (unsigned long long*)meta;
   uint8_t* d_dah = meta + 256;
+  uint8_t* d_dnodes = meta + 512;
   auto level = [&](int h) { return d_levels + square_level_offset(L, h) * CDA_REC_BYTES; };
   hipStream_t s = c->stream;
   int rc;
@@ -111,26 +116,29 @@ int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_
     if (launch_nmt_level(h == 1 ? d_leaf : level(h - 1), level(h), h == 1, (int)k, 1, h, s)) return CDA_E_DEVICE;
   }
   uint8_t* d_roots = level(L);  // 2w root records, rows then columns
-  {
+  {  // the DAH, and from the same launch the RFC-6962 tree over rowRoots ‖ colRoots, which stays with the square: a
+     // share proof's leaf hashes and aunts
     ProfScope ps(c, "dah", s);
-    const int lr = launch_dah(d_roots, d_dah, (int)(2 * w), 1, s);
+    const int lr = launch_dah_tree(d_roots, d_dah, d_dnodes, (int)(2 * w), s);
     if (lr) return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;
   }
-  const size_t roots_b = (size_t)2 * w * CDA_REC_BYTES;
-  std::vector<uint8_t> recs(roots_b);
+  // the root records end the level area and the status word and the DAH follow within a few hundred bytes: one copy
+  // brings all three back (three small pageable copies cost more than the launch that keeps the data-root tree)
+  const size_t meta_at = (size_t)(meta - d_roots), back_b = meta_at + 288;
+  std::vector<uint8_t> recs(back_b);
   uint64_t st = 0;
-  if (!dev_ok(c, hipMemcpyAsync(recs.data(), d_roots, roots_b, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipMemcpyAsync(dah, d_dah, 32, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipMemcpyAsync(&st, d_status, 8, hipMemcpyDeviceToHost, s), "D2H") ||
+  if (!dev_ok(c, hipMemcpyAsync(recs.data(), d_roots, back_b, hipMemcpyDeviceToHost, s), "D2H") ||
       !dev_ok(c, hipStreamSynchronize(s), "sync"))
     return CDA_E_DEVICE;
+  memcpy(&st, recs.data() + meta_at, 8);
+  memcpy(dah, recs.data() + meta_at + 256, 32);
   flush_profile(c);
   pack_roots(recs.data(), w, row_roots);
   pack_roots(recs.data() + (size_t)w * CDA_REC_BYTES, w, col_roots);
   if ((rc = map_status(st, 0, err))) return rc;
   sq->c = c;
   sq->k = k;
-  sq->view = SquareView{d_eds, d_leaf, d_levels, L};
+  sq->view = SquareView{d_eds, d_leaf, d_levels, L, d_dnodes};
   c->squares.push_back(sq);
   own.sq = nullptr;
   *out = sq;
@@ -281,6 +289,177 @@ int cda_nmt_verify_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, con
   ProfScope ps(c, "nmt_verify", dl.s);
   // the descriptors are device memory: whether any proof has more than one leaf is not known here
   return launch_nmt_verify(a, true, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_square_share_proofs(cda_square* sq, uint32_t nq, const cda_share_range* q, uint32_t max_nodes,
+                            uint32_t rows_cap, uint32_t* row_off, cda_share_row* rows, uint8_t* nodes,
+                            uint8_t* row_roots, uint8_t* leaf_hashes, uint8_t* aunts, uint8_t* shares_or_null,
+                            uint64_t shares_cap, uint8_t* data_root) {
+  cda_ctx* c = sq ? sq->c : nullptr;
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;  // null, or a square whose context was freed
+  if (nq == 0) return CDA_OK;
+  if (!q || !row_off || !rows || !nodes || !row_roots || !leaf_hashes || !aunts || !data_root) return CDA_E_ARG;
+  if (nq > (1u << 24)) return CDA_E_UNSUPPORTED;
+  const uint32_t k = sq->k, naunts = (uint32_t)sq->view.log2w + 1;
+  if (max_nodes < 2 * (uint32_t)sq->view.log2w) return CDA_E_ARG;
+  // the queries against the square, and the sizes of the outputs: where each query's row records and shares start
+  std::vector<uint32_t> off(2 * (size_t)nq + 1);  // row_off (nq + 1) | share_off (nq)
+  uint64_t nrows = 0, nshares = 0;
+  for (uint32_t i = 0; i < nq; i++) {
+    if (q[i].start >= q[i].end || q[i].end > k * k) return CDA_E_ARG;
+    if (nrows > 0xFFFFFFFFull || nshares > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;
+    off[i] = (uint32_t)nrows;
+    off[nq + 1 + i] = (uint32_t)nshares;
+    nrows += (q[i].end - 1) / k - q[i].start / k + 1;
+    nshares += q[i].end - q[i].start;
+  }
+  if (nrows > rows_cap || (shares_or_null && nshares * CDA_SHARE > shares_cap)) return CDA_E_ARG;
+  if ((nrows * max_nodes) >> 32 || (nrows * naunts) >> 32 || nshares > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;
+  off[nq] = (uint32_t)nrows;
+  Lock l(c);
+  hipStream_t s = c->stream;
+  // staging in the context's workspace: queries | offsets | row records | row roots | leaf hashes | aunts, the nodes,
+  // the shares
+  const size_t q_b = align256((size_t)nq * sizeof(cda_share_range)), off_b = align256(off.size() * 4);
+  const size_t rows_b = align256(nrows * sizeof(cda_share_row)), roots_b = align256(nrows * CDA_NODE_SIZE);
+  const size_t lh_b = align256(nrows * 32), aunts_b = nrows * naunts * 32;
+  const size_t nodes_b = nrows * max_nodes * CDA_NODE_SIZE, shares_b = shares_or_null ? nshares * CDA_SHARE : 0;
+  int rc;
+  if ((rc = ensure(c, c->plan, q_b + off_b + rows_b + roots_b + lh_b + aunts_b)) ||
+      (rc = ensure(c, c->nodes, nodes_b)) || (shares_b && (rc = ensure(c, c->payload, shares_b))))
+    return rc;
+  uint8_t* base = (uint8_t*)c->plan.p;
+  cda_share_range* d_q = (cda_share_range*)base;
+  uint32_t* d_off = (uint32_t*)(base + q_b);
+  ShareProofsOut o{};
+  o.rows = (cda_share_row*)(base + q_b + off_b);
+  o.row_roots = base + q_b + off_b + rows_b;
+  o.leaf_hashes = o.row_roots + roots_b;
+  o.aunts = o.leaf_hashes + lh_b;
+  o.nodes = (uint8_t*)c->nodes.p;
+  o.shares = shares_b ? (uint8_t*)c->payload.p : nullptr;
+  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_share_range), hipMemcpyHostToDevice, s), "H2D") ||
+      !dev_ok(c, hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s), "H2D"))
+    return CDA_E_DEVICE;
+  {
+    ProfScope ps(c, "square_share_proofs", s);
+    if (launch_square_share_proofs(sq->view, d_q, nq, d_off, d_off + nq + 1, (uint32_t)nrows, max_nodes, o, s))
+      return CDA_E_DEVICE;
+  }
+  const uint8_t* d_root = sq->view.dah_nodes + (2 * (size_t)(4 * k) - 2) * 32;  // the last node of the tree
+  if (!copy_any(c, row_off, d_off, ((size_t)nq + 1) * 4, s) ||
+      !copy_any(c, rows, o.rows, nrows * sizeof(cda_share_row), s) || !copy_any(c, nodes, o.nodes, nodes_b, s) ||
+      !copy_any(c, row_roots, o.row_roots, nrows * CDA_NODE_SIZE, s) ||
+      !copy_any(c, leaf_hashes, o.leaf_hashes, nrows * 32, s) || !copy_any(c, aunts, o.aunts, aunts_b, s) ||
+      !copy_any(c, shares_or_null, o.shares, shares_b, s) || !copy_any(c, data_root, d_root, 32, s) ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_share_proofs_validate(cda_ctx* c, uint32_t nproofs, const cda_share_proof_desc* descs,
+                              const cda_share_row* rows, const uint8_t* row_roots, const uint8_t* leaf_hashes,
+                              uint32_t nrows, const uint8_t* nodes, uint32_t nnodes, const uint8_t* aunts,
+                              uint32_t naunts, const uint8_t* leaves, uint32_t nleaves, const uint8_t* data_roots,
+                              uint32_t nroots, int32_t* verdicts) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!descs || !verdicts || (nrows && (!rows || !row_roots || !leaf_hashes)) || (nnodes && !nodes) ||
+      (naunts && !aunts) || (nleaves && !leaves) || (nroots && !data_roots))
+    return CDA_E_ARG;
+  Lock l(c);
+  hipStream_t s = c->stream;
+  // descriptors | row records | row roots | leaf hashes | aunts | data roots | verdicts | the kernels' workspace
+  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_share_proof_desc));
+  const size_t rows_b = align256((size_t)nrows * sizeof(cda_share_row));
+  const size_t rr_b = align256((size_t)nrows * CDA_NODE_SIZE), lh_b = align256((size_t)nrows * 32);
+  const size_t aunts_b = align256((size_t)naunts * 32), dr_b = align256((size_t)nroots * 32);
+  const size_t ver_b = align256((size_t)nproofs * 4), ws_b = validate_workspace_bytes(nproofs, nrows);
+  const size_t nodes_b = (size_t)nnodes * CDA_NODE_SIZE, leaves_b = (size_t)nleaves * CDA_SHARE;
+  int rc;
+  if ((rc = ensure(c, c->plan, desc_b + rows_b + rr_b + lh_b + aunts_b + dr_b + ver_b + ws_b)) ||
+      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
+    return rc;
+  uint8_t* p = (uint8_t*)c->plan.p;
+  auto up = [&](const void* src, size_t n, size_t slot) -> uint8_t* {  // null: the copy failed
+    uint8_t* at = p;
+    p += slot;
+    if (n && !dev_ok(c, hipMemcpyAsync(at, src, n, hipMemcpyHostToDevice, s), "H2D")) return nullptr;
+    return at;
+  };
+  ValidateArgs a{};
+  a.nproofs = nproofs;
+  a.nrows = nrows;
+  a.nnodes = nnodes;
+  a.naunts = naunts;
+  a.nleaves = nleaves;
+  a.nroots = nroots;
+  if (!(a.descs = (const cda_share_proof_desc*)up(descs, (size_t)nproofs * sizeof(cda_share_proof_desc), desc_b)) ||
+      !(a.rows = (const cda_share_row*)up(rows, (size_t)nrows * sizeof(cda_share_row), rows_b)) ||
+      !(a.row_roots = up(row_roots, (size_t)nrows * CDA_NODE_SIZE, rr_b)) ||
+      !(a.leaf_hashes = up(leaf_hashes, (size_t)nrows * 32, lh_b)) ||
+      !(a.aunts = up(aunts, (size_t)naunts * 32, aunts_b)) || !(a.data_roots = up(data_roots, (size_t)nroots * 32, dr_b)))
+    return CDA_E_DEVICE;
+  a.verdicts = (int32_t*)p;
+  validate_workspace_bind(a, p + ver_b);
+  a.nodes = (const uint8_t*)c->nodes.p;
+  a.leaves = (const uint8_t*)c->payload.p;
+  if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
+  if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
+  {
+    ProfScope ps(c, "share_proofs_validate", s);
+    if (launch_share_proofs_validate(a, s)) return CDA_E_DEVICE;
+  }
+  if (!dev_ok(c, hipMemcpyAsync(verdicts, a.verdicts, (size_t)nproofs * 4, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_share_proofs_validate_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, const void* d_rows,
+                                     const void* d_row_roots, const void* d_leaf_hashes, uint32_t nrows,
+                                     const void* d_nodes, uint32_t nnodes, const void* d_aunts, uint32_t naunts,
+                                     const void* d_leaves, uint32_t nleaves, const void* d_data_roots,
+                                     uint32_t nroots, void* d_verdicts, void* stream) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!d_descs || !d_verdicts || (nrows && (!d_rows || !d_row_roots || !d_leaf_hashes)) || (nnodes && !d_nodes) ||
+      (naunts && !d_aunts) || (nleaves && !d_leaves) || (nroots && !d_data_roots))
+    return CDA_E_ARG;
+  // shares are read 16 bytes at a time, row records hold 64-bit fields, everything else is read in 4-byte words
+  if (((uintptr_t)d_leaves & 15) || ((uintptr_t)d_rows & 7) ||
+      (((uintptr_t)d_descs | (uintptr_t)d_row_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_nodes |
+        (uintptr_t)d_aunts | (uintptr_t)d_data_roots | (uintptr_t)d_verdicts) & 3))
+    return CDA_E_ARG;
+  ValidateArgs a{};
+  a.descs = (const cda_share_proof_desc*)d_descs;
+  a.rows = (const cda_share_row*)d_rows;
+  a.row_roots = (const uint8_t*)d_row_roots;
+  a.leaf_hashes = (const uint8_t*)d_leaf_hashes;
+  a.nodes = (const uint8_t*)d_nodes;
+  a.aunts = (const uint8_t*)d_aunts;
+  a.leaves = (const uint8_t*)d_leaves;
+  a.data_roots = (const uint8_t*)d_data_roots;
+  a.verdicts = (int32_t*)d_verdicts;
+  a.nproofs = nproofs;
+  a.nrows = nrows;
+  a.nnodes = nnodes;
+  a.naunts = naunts;
+  a.nleaves = nleaves;
+  a.nroots = nroots;
+  DevLock dl(c, (hipStream_t)stream);
+  if (int rc = ensure(c, c->plan, validate_workspace_bytes(nproofs, nrows))) return rc;
+  validate_workspace_bind(a, c->plan.p);
+  ProfScope ps(c, "share_proofs_validate", dl.s);
+  return launch_share_proofs_validate(a, dl.s) ? CDA_E_DEVICE : CDA_OK;
   CDA_API_CATCH(c)
 }
 

@@ -13,11 +13,14 @@ namespace cda {
 //   leaf    (2k)^2 leaf records of 96 B, cell-major (a cell's leaf is the same node in its row and its column tree)
 //   levels  the records of tree levels 1 .. log2(2k), each level [tree][node] with trees 0..2k-1 the rows and
 //           2k..4k-1 the columns (launch_nmt_level's layout); level h starts square_level_offset(log2w, h) records in
+//   dah_nodes  the RFC-6962 tree over rowRoots ‖ colRoots, 8k - 1 digests of 32 B: the 4k leaf hashes, then each
+//           level, the data root last (cda_extend_commit_nodes' dah_nodes)
 struct SquareView {
   const uint8_t* eds;
   const uint8_t* leaf;
   const uint8_t* levels;
   int log2w;
+  const uint8_t* dah_nodes;
 };
 // records of levels 1 .. h - 1 of the 4k trees: 2w (w / 2 + .. + w >> (h - 1))
 __host__ __device__ inline size_t square_level_offset(int log2w, int h) {
@@ -39,6 +42,49 @@ struct VerifyArgs {
 // d_share_off (nq words of scratch) and d_shares: both null when the cells are not wanted
 int launch_square_prove(const SquareView& v, const cda_range_query* d_q, uint32_t nq, uint32_t max_nodes,
                         int32_t* d_counts, uint8_t* d_nodes, uint32_t* d_share_off, uint8_t* d_shares, hipStream_t s);
+// cda_square_share_proofs' outputs, all device memory (include/cda.h); shares null when the cells are not wanted
+struct ShareProofsOut {
+  cda_share_row* rows;
+  uint8_t* nodes;
+  uint8_t* row_roots;
+  uint8_t* leaf_hashes;
+  uint8_t* aunts;
+  uint8_t* shares;
+};
+// d_row_off: nq + 1 words, d_share_off: nq words (the shares of the queries before q); nrows = d_row_off[nq]
+int launch_square_share_proofs(const SquareView& v, const cda_share_range* d_q, uint32_t nq, const uint32_t* d_row_off,
+                               const uint32_t* d_share_off, uint32_t nrows, uint32_t max_nodes,
+                               const ShareProofsOut& out, hipStream_t s);
+
+// cda_share_proofs_validate's arguments, all device memory (include/cda.h), and its workspace
+struct ValidateArgs {
+  const cda_share_proof_desc* descs;
+  const cda_share_row* rows;
+  const uint8_t* row_roots;
+  const uint8_t* leaf_hashes;
+  const uint8_t* nodes;
+  const uint8_t* aunts;
+  const uint8_t* leaves;
+  const uint8_t* data_roots;
+  int32_t* verdicts;
+  uint32_t nproofs, nrows, nnodes, naunts, nleaves, nroots;
+  // workspace: per proof the verdict of the counting checks; per row record the proof that owns it (~0: none), how
+  // many proofs claim it, the NMT leg's descriptor, namespace and verdict, the row-proof leg's verdict
+  int32_t* pre;
+  uint32_t* owner;
+  uint32_t* claims;
+  cda_nmt_proof_desc* nmt_descs;
+  uint8_t* nmt_ns;
+  uint8_t* nmt_ok;
+  uint8_t* row_ok;
+};
+size_t validate_workspace_bytes(uint32_t nproofs, uint32_t nrows);
+// points a's workspace fields into `ws` (validate_workspace_bytes, 256-byte aligned)
+void validate_workspace_bind(ValidateArgs& a, void* ws);
+// the three legs: counting checks and NMT descriptors, launch_nmt_verify over the row records, one Proof.Verify per
+// lane; then the per-proof verdict
+int launch_share_proofs_validate(const ValidateArgs& a, hipStream_t s);
+
 // ranges = false: no descriptor has more than one leaf (the kernel of the longer proofs is not launched)
 int launch_nmt_verify(const VerifyArgs& a, bool ranges, hipStream_t s);
 

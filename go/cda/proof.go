@@ -157,3 +157,222 @@ func ShareInclusionProof(ctx *Context, s [][]byte, start, end int) (*ShareProofP
 	}
 	return out, nil
 }
+
+// RetainedSquare is one extended block kept on the device (cda_square_open): the EDS, every node of its 4k trees and
+// the RFC-6962 tree over rowRoots ‖ colRoots.  It answers any number of share-range proofs per call without
+// extending or hashing again.  Close it when the block is no longer served; closing after the context was closed is
+// safe.
+type RetainedSquare struct {
+	h        *C.cda_square
+	K        int
+	RowRoots [][]byte
+	ColRoots [][]byte
+	DataHash []byte
+}
+
+// OpenSquare extends and commits the k*k shares once (da.ExtendShares + NewDataAvailabilityHeader) and keeps the
+// square on the device.
+func OpenSquare(ctx *Context, s [][]byte) (*RetainedSquare, error) {
+	if !isPowerOfTwo(len(s)) {
+		return nil, fmt.Errorf("number of shares is not a power of 2: got %d", len(s))
+	}
+	flat, n, err := flatten(s)
+	if err != nil {
+		return nil, err
+	}
+	k := squareSize(len(s))
+	w := 2 * k
+	rows := make([]byte, w*NodeSize)
+	cols := make([]byte, w*NodeSize)
+	dah := make([]byte, 32)
+	var h *C.cda_square
+	var info C.cda_err_info
+	rc := C.cda_square_open(ctx.c, C.uint32_t(len(s)), C.uint32_t(n), ptr(flat), &h, ptr(rows), ptr(cols), ptr(dah),
+		&info)
+	if rc != 0 {
+		return nil, toErr(rc, &info)
+	}
+	return &RetainedSquare{h: h, K: k, RowRoots: split(rows, w), ColRoots: split(cols, w), DataHash: dah}, nil
+}
+
+// Close releases the square's device memory.
+func (sq *RetainedSquare) Close() {
+	if sq.h != nil {
+		C.cda_square_close(sq.h)
+		sq.h = nil
+	}
+}
+
+// ShareRange is shares.Range over the ODS, row-major: [Start, End).
+type ShareRange struct {
+	Start, End int
+}
+
+// SquareShareProof is one proof of a ShareProofs batch: the proved shares (ShareProof.Data) and the parts of its rows.
+type SquareShareProof struct {
+	Data [][]byte
+	ShareProofParts
+}
+
+// ShareProofs is pkg/proof NewShareInclusionProof (proof.go:55-167) for every range from ONE launch
+// (cda_square_share_proofs): each proof's NMT range proofs, row roots and the row roots' proofs in the data root are
+// gathered from the retained nodes.
+func (sq *RetainedSquare) ShareProofs(ranges []ShareRange) ([]SquareShareProof, error) {
+	if sq.h == nil {
+		return nil, fmt.Errorf("cda: square is closed")
+	}
+	if len(ranges) == 0 {
+		return nil, nil
+	}
+	k := sq.K
+	lg := 0
+	for 1<<lg < 2*k {
+		lg++
+	}
+	maxNodes, naunts := 2*lg, lg+1
+	if maxNodes == 0 {
+		maxNodes = 1
+	}
+	q := make([]C.cda_share_range, len(ranges))
+	nrows, nshares := 0, 0
+	for i, r := range ranges {
+		if r.Start < 0 || r.Start >= r.End || r.End > k*k {
+			return nil, fmt.Errorf("cda: share range [%d, %d) outside the %d x %d square", r.Start, r.End, k, k)
+		}
+		q[i].start, q[i].end = C.uint32_t(r.Start), C.uint32_t(r.End)
+		nrows += (r.End-1)/k - r.Start/k + 1
+		nshares += r.End - r.Start
+	}
+	rowOff := make([]uint32, len(ranges)+1)
+	recs := make([]C.cda_share_row, nrows)
+	nodes := make([]byte, nrows*maxNodes*NodeSize)
+	rr := make([]byte, nrows*NodeSize)
+	lh := make([]byte, nrows*32)
+	au := make([]byte, nrows*naunts*32)
+	shares := make([]byte, nshares*ShareSize)
+	root := make([]byte, 32)
+	rc := C.cda_square_share_proofs(sq.h, C.uint32_t(len(q)), &q[0], C.uint32_t(maxNodes), C.uint32_t(nrows),
+		(*C.uint32_t)(unsafe.Pointer(&rowOff[0])), &recs[0], ptr(nodes), ptr(rr), ptr(lh), ptr(au), ptr(shares),
+		C.uint64_t(len(shares)), ptr(root))
+	if rc != 0 {
+		return nil, toErr(rc, nil)
+	}
+	out := make([]SquareShareProof, len(ranges))
+	cursor := 0
+	for i, r := range ranges {
+		p := &out[i]
+		p.DataRoot = root
+		p.Data = split(shares[cursor*ShareSize:(cursor+r.End-r.Start)*ShareSize], r.End-r.Start)
+		cursor += r.End - r.Start
+		lo, hi := int(rowOff[i]), int(rowOff[i+1])
+		p.StartRow, p.EndRow = int(recs[lo].row), int(recs[hi-1].row)
+		for j := lo; j < hi; j++ {
+			rec := &recs[j]
+			part := RowProofPart{
+				Row:      int(rec.row),
+				RowRoot:  rr[j*NodeSize : (j+1)*NodeSize : (j+1)*NodeSize],
+				Total:    int64(rec.total),
+				LeafHash: lh[j*32 : (j+1)*32 : (j+1)*32],
+				Start:    int32(rec.nmt_start),
+				End:      int32(rec.nmt_end),
+			}
+			for a := 0; a < int(rec.naunts); a++ {
+				o := (int(rec.aunt_off) + a) * 32
+				part.Aunts = append(part.Aunts, au[o:o+32:o+32])
+			}
+			for t := 0; t < int(rec.nnodes); t++ {
+				o := (int(rec.node_off) + t) * NodeSize
+				part.Nodes = append(part.Nodes, nodes[o:o+NodeSize:o+NodeSize])
+			}
+			p.Rows = append(p.Rows, part)
+		}
+	}
+	return out, nil
+}
+
+// ShareProofVerdict is the first check of ShareProof.Validate (share_proof.go:16-51) that a proof fails, 0 if none
+// (the CDA_SP_* codes of cda.h).
+type ShareProofVerdict int32
+
+// ValidateShareProofs is ShareProof.Validate of a batch on the GPU (cda_share_proofs_validate): proof i under the
+// 29-byte namespace namespaces[i] against dataRoots[i].  A false proof is a verdict, never an error.
+func ValidateShareProofs(ctx *Context, proofs []SquareShareProof, namespaces [][]byte,
+	dataRoots [][]byte) ([]ShareProofVerdict, error) {
+	if len(proofs) == 0 {
+		return nil, nil
+	}
+	if len(namespaces) != len(proofs) || len(dataRoots) != len(proofs) {
+		return nil, fmt.Errorf("cda: %d proofs, %d namespaces, %d data roots", len(proofs), len(namespaces),
+			len(dataRoots))
+	}
+	descs := make([]C.cda_share_proof_desc, len(proofs))
+	var recs []C.cda_share_row
+	var rr, lh, nodes, aunts, leaves, roots []byte
+	nnodes, naunts, nleaves := 0, 0, 0
+	for i := range proofs {
+		p := &proofs[i]
+		if len(namespaces[i]) != NamespaceSize || len(dataRoots[i]) != 32 {
+			return nil, fmt.Errorf("cda: proof %d: namespace of %d bytes, data root of %d", i, len(namespaces[i]),
+				len(dataRoots[i]))
+		}
+		d := &descs[i]
+		d.row_off = C.uint32_t(len(recs))
+		d.nshare_proofs, d.nrow_roots, d.nrow_proofs = C.uint32_t(len(p.Rows)), C.uint32_t(len(p.Rows)),
+			C.uint32_t(len(p.Rows))
+		d.leaf_off, d.nleaves = C.uint32_t(nleaves), C.uint32_t(len(p.Data))
+		d.start_row, d.end_row = C.uint32_t(p.StartRow), C.uint32_t(p.EndRow)
+		d.data_root = C.uint32_t(i)
+		for j := 0; j < NamespaceSize; j++ {
+			d.ns[j] = C.uint8_t(namespaces[i][j])
+		}
+		roots = append(roots, dataRoots[i]...)
+		for _, s := range p.Data {
+			if len(s) != ShareSize {
+				return nil, fmt.Errorf("cda: proof %d: share of %d bytes", i, len(s))
+			}
+			leaves = append(leaves, s...)
+		}
+		nleaves += len(p.Data)
+		for _, row := range p.Rows {
+			if len(row.RowRoot) != NodeSize || len(row.LeafHash) != 32 {
+				return nil, fmt.Errorf("cda: proof %d: row root of %d bytes, leaf hash of %d", i, len(row.RowRoot),
+					len(row.LeafHash))
+			}
+			var rec C.cda_share_row
+			rec.nmt_start, rec.nmt_end = C.int32_t(row.Start), C.int32_t(row.End)
+			rec.node_off, rec.nnodes = C.uint32_t(nnodes), C.uint32_t(len(row.Nodes))
+			rec.total, rec.index = C.int64_t(row.Total), C.int64_t(row.Row)
+			rec.aunt_off, rec.naunts = C.uint32_t(naunts), C.uint32_t(len(row.Aunts))
+			rec.row = C.uint32_t(row.Row)
+			recs = append(recs, rec)
+			rr = append(rr, row.RowRoot...)
+			lh = append(lh, row.LeafHash...)
+			for _, x := range row.Nodes {
+				if len(x) != NodeSize {
+					return nil, fmt.Errorf("cda: proof %d: node of %d bytes", i, len(x))
+				}
+				nodes = append(nodes, x...)
+			}
+			for _, x := range row.Aunts {
+				if len(x) != 32 {
+					return nil, fmt.Errorf("cda: proof %d: aunt of %d bytes", i, len(x))
+				}
+				aunts = append(aunts, x...)
+			}
+			nnodes += len(row.Nodes)
+			naunts += len(row.Aunts)
+		}
+	}
+	verdicts := make([]ShareProofVerdict, len(proofs))
+	var recp *C.cda_share_row
+	if len(recs) > 0 {
+		recp = &recs[0]
+	}
+	rc := C.cda_share_proofs_validate(ctx.c, C.uint32_t(len(descs)), &descs[0], recp, ptr(rr), ptr(lh),
+		C.uint32_t(len(recs)), ptr(nodes), C.uint32_t(nnodes), ptr(aunts), C.uint32_t(naunts), ptr(leaves),
+		C.uint32_t(nleaves), ptr(roots), C.uint32_t(len(proofs)), (*C.int32_t)(unsafe.Pointer(&verdicts[0])))
+	if rc != 0 {
+		return nil, toErr(rc, nil)
+	}
+	return verdicts, nil
+}

@@ -302,7 +302,8 @@ int cda_share_inclusion_proof(cda_ctx* ctx, uint32_t count, uint32_t share_len, 
 /* ---- sample proofs: prove any EDS cell, verify proved cells in batches ---- */
 /* A retained square: the block is extended once and the EDS with every node of its 4k trees stays in
  * device memory that belongs to the handle (never the context's workspace: other calls on the context
- * leave it untouched).  Calls on a handle take its context's lock.  cda_free of a context with open
+ * leave it untouched), and with them the RFC-6962 tree over rowRoots ‖ colRoots (8k - 1 nodes of 32 B, the layout of
+ * cda_extend_commit_nodes' dah_nodes) that cda_square_share_proofs reads leaf hashes and aunts from.  Calls on a handle take its context's lock.  cda_free of a context with open
  * squares releases their device memory; such a handle stays valid for cda_square_close only (every
  * other call on it returns CDA_E_ARG), so close after free never touches the device. */
 typedef struct cda_square cda_square;
@@ -344,6 +345,81 @@ int cda_nmt_verify(cda_ctx* ctx, uint32_t nproofs, const cda_nmt_proof_desc* des
 int cda_nmt_verify_device(cda_ctx* ctx, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
                           const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
                           const void* d_leaves, uint32_t nleaves_total, void* d_ok, void* stream);
+
+/* ---- share proofs to the data root: many per launch from a retained square, batched Validate ---- */
+/* ODS shares [start, end), row-major, 0 <= start < end <= k*k: the range ParseNamespace has validated
+ * (pkg/proof/querier.go:126-158). */
+typedef struct {
+  uint32_t start, end;
+} cda_share_range;
+/* One row of a ShareProof: the NMTProof of the row's shares (ShareProof.ShareProofs[i]) and the merkle Proof of
+ * the row root in the data root (RowProof.Proofs[i]).  Row record r goes with row_roots[r] (90 B, RowProof.RowRoots)
+ * and leaf_hashes[r] (32 B, Proof.LeafHash); its nodes and aunts are addressed in the flat arrays. */
+typedef struct {
+  int32_t nmt_start, nmt_end; /* NMTProof.Start / End (signed, as in proof.pb.go) */
+  uint32_t node_off, nnodes;  /* NMTProof.Nodes = nodes[node_off, node_off + nnodes) of 90 B */
+  int64_t total, index;       /* Proof.Total / Index */
+  uint32_t aunt_off, naunts;  /* Proof.Aunts = aunts[aunt_off, aunt_off + naunts) of 32 B, bottom-up */
+  uint32_t row;               /* the row of the square (cda_square_share_proofs; cda_share_proofs_validate ignores it) */
+  uint32_t pad_;
+} cda_share_row;
+/* pkg/proof NewShareInclusionProof (proof.go:55-167) for nq ranges of a retained square in one launch: nothing is
+ * extended or hashed again.  Query q proves rows start / k .. (end - 1) / k (proof.go:61-64); its row records are
+ * rows[row_off[q], row_off[q + 1]) (row_off: nq + 1 words).  Per row the NMT range is [start % k, k) on the first
+ * row, [0, k) between, [0, (end - 1) % k + 1) on the last (proof.go:129-139); record r has node_off = r * max_nodes
+ * (the slots after its nnodes nodes are zero), aunt_off = r * log2(4k), naunts = log2(4k), total = 4k, index = row
+ * (merkle.ProofsFromByteSlices over rowRoots ‖ colRoots, proof.go:82-93).  Capacities: rows_cap row records in rows /
+ * nodes (x max_nodes x 90 B) / row_roots (x 90) / leaf_hashes (x 32) / aunts (x log2(4k) x 32); shares_cap bytes in
+ * shares_or_null, which receives the proved shares (ShareProof.Data) packed in query order.  data_root: 32 B, once.
+ * CDA_E_ARG before any launch for a range outside the square, max_nodes < 2 log2(2k) or a capacity too small.
+ * q is host memory; every output may be host or device memory. */
+int cda_square_share_proofs(cda_square* sq, uint32_t nq, const cda_share_range* q, uint32_t max_nodes,
+                            uint32_t rows_cap, uint32_t* row_off, cda_share_row* rows, uint8_t* nodes,
+                            uint8_t* row_roots, uint8_t* leaf_hashes, uint8_t* aunts, uint8_t* shares_or_null,
+                            uint64_t shares_cap, uint8_t* data_root);
+
+/* One ShareProof of a cda_share_proofs_validate batch over flat arrays: ShareProofs / RowRoots / Proofs are the first
+ * nshare_proofs / nrow_roots / nrow_proofs of the row records from row_off (a well-formed proof has the three equal),
+ * Data = leaves[leaf_off, leaf_off + nleaves) of 512 B, the root to validate against = data_roots[data_root]. */
+typedef struct {
+  uint32_t row_off;
+  uint32_t nshare_proofs, nrow_roots, nrow_proofs;
+  uint32_t leaf_off, nleaves;
+  uint32_t start_row, end_row; /* RowProof.StartRow / EndRow */
+  uint32_t data_root;
+  uint8_t ns[29]; /* NamespaceVersion ‖ NamespaceID */
+  uint8_t pad_[3];
+} cda_share_proof_desc;
+/* Verdicts: 0, or the first check of ShareProof.Validate that fails, in its order (share_proof.go:16-51,
+ * RowProof.Validate row_proof.go:13-24). */
+enum {
+  CDA_SP_VALID = 0,
+  CDA_SP_PROOF_COUNT = 1, /* "the number of share proofs ... must equal the number of row roots" */
+  CDA_SP_DATA_COUNT = 2,  /* "the number of shares ... must equal the number of shares in share proofs" */
+  CDA_SP_NEG_START = 3,   /* "proof index cannot be negative" */
+  CDA_SP_EMPTY_RANGE = 4, /* "proof total must be positive" */
+  CDA_SP_ROW_COUNT = 5,   /* "the number of rows ... must equal the number of row roots" */
+  CDA_SP_ROW_PROOFS = 6,  /* "the number of proofs ... must equal the number of row roots" */
+  CDA_SP_ROW_PROOF = 7,   /* "row proof failed to verify" (merkle Proof.Verify of a row root, row_proof.go:26-48) */
+  CDA_SP_SHARE_PROOF = 8, /* "share proof failed to verify" (nmt VerifyInclusion of a row, share_proof.go:53-82) */
+  CDA_SP_MALFORMED = 9,   /* a descriptor points outside the totals, or shares row records with another proof:
+                             nothing is read through it */
+};
+/* Batched ShareProof.Validate: verdicts[p] (int32) for proof p.  A false proof is a verdict, never an error code.
+ * The arrays cda_square_share_proofs writes are accepted as they lie.  nrows / nnodes / naunts / nleaves / nroots
+ * are the totals of rows (and row_roots, leaf_hashes) / nodes / aunts / leaves / data_roots. */
+int cda_share_proofs_validate(cda_ctx* ctx, uint32_t nproofs, const cda_share_proof_desc* descs,
+                              const cda_share_row* rows, const uint8_t* row_roots, const uint8_t* leaf_hashes,
+                              uint32_t nrows, const uint8_t* nodes, uint32_t nnodes, const uint8_t* aunts,
+                              uint32_t naunts, const uint8_t* leaves, uint32_t nleaves, const uint8_t* data_roots,
+                              uint32_t nroots, int32_t* verdicts);
+/* The same with every pointer in device memory (d_leaves 16-byte, d_rows 8-byte, the others 4-byte aligned, else
+ * CDA_E_ARG), asynchronous on `stream`; every check is made in the kernels.  Uses the context's workspace. */
+int cda_share_proofs_validate_device(cda_ctx* ctx, uint32_t nproofs, const void* d_descs, const void* d_rows,
+                                     const void* d_row_roots, const void* d_leaf_hashes, uint32_t nrows,
+                                     const void* d_nodes, uint32_t nnodes, const void* d_aunts, uint32_t naunts,
+                                     const void* d_leaves, uint32_t nleaves, const void* d_data_roots,
+                                     uint32_t nroots, void* d_verdicts, void* stream);
 
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
