@@ -58,6 +58,7 @@ EXPORTS = [
     "cda_multi_init_replicas", "cda_set_option", "cda_host_register", "cda_host_unregister",
     "cda_square_open", "cda_square_close", "cda_square_prove", "cda_nmt_verify", "cda_nmt_verify_device",
     "cda_square_share_proofs", "cda_share_proofs_validate", "cda_share_proofs_validate_device",
+    "cda_square_prove_namespace", "cda_nmt_verify_namespace", "cda_nmt_verify_namespace_device",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -113,6 +114,29 @@ class ShareProofDesc(ctypes.Structure):
                 ("ns", ctypes.c_uint8 * 29), ("pad_", ctypes.c_uint8 * 3)]
 
 
+class NamespaceQuery(ctypes.Structure):
+    """cda_namespace_query: tree (axis, index).ProveNamespace(ns)."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("ns", ctypes.c_uint8 * 29),
+                ("pad_", ctypes.c_uint8 * 3)]
+
+
+class NamespaceResult(ctypes.Structure):
+    """cda_namespace_result: what cda_square_prove_namespace found for one query."""
+    _fields_ = [("kind", ctypes.c_uint32), ("start", ctypes.c_uint32), ("end", ctypes.c_uint32),
+                ("nnodes", ctypes.c_uint32), ("share_off", ctypes.c_uint32), ("nshares", ctypes.c_uint32)]
+
+
+class NmtNsProofDesc(ctypes.Structure):
+    """cda_nmt_ns_proof_desc: one proof of a cda_nmt_verify_namespace batch."""
+    _fields_ = [("start", ctypes.c_uint32), ("end", ctypes.c_uint32), ("node_off", ctypes.c_uint32),
+                ("nnodes", ctypes.c_uint32), ("leaf_off", ctypes.c_uint32), ("nleaves", ctypes.c_uint32),
+                ("root", ctypes.c_uint32), ("leaf_hash", ctypes.c_uint32)]
+
+
+# cda_namespace_result.kind (include/cda.h CDA_NSP_*), and "no leaf hash" of a cda_nmt_ns_proof_desc
+NSP_EMPTY, NSP_INCLUSION, NSP_ABSENCE = range(3)
+NO_LEAF_HASH = 0xFFFFFFFF
+
 # ShareProof.Validate's checks in its order (include/cda.h CDA_SP_*)
 SP_VALID, SP_PROOF_COUNT, SP_DATA_COUNT, SP_NEG_START, SP_EMPTY_RANGE, SP_ROW_COUNT, SP_ROW_PROOFS, SP_ROW_PROOF, \
     SP_SHARE_PROOF, SP_MALFORMED = range(10)
@@ -126,6 +150,11 @@ SHARE_PROOF_DESC_DTYPE = np.dtype([("row_off", "<u4"), ("nshare_proofs", "<u4"),
                                    ("nrow_proofs", "<u4"), ("leaf_off", "<u4"), ("nleaves", "<u4"),
                                    ("start_row", "<u4"), ("end_row", "<u4"), ("data_root", "<u4"),
                                    ("ns", "u1", (29,)), ("pad_", "u1", (3,))])
+NAMESPACE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("ns", "u1", (29,)), ("pad_", "u1", (3,))])
+NAMESPACE_RESULT_DTYPE = np.dtype([("kind", "<u4"), ("start", "<u4"), ("end", "<u4"), ("nnodes", "<u4"),
+                                   ("share_off", "<u4"), ("nshares", "<u4")])
+NMT_NS_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
+                                    ("leaf_off", "<u4"), ("nleaves", "<u4"), ("root", "<u4"), ("leaf_hash", "<u4")])
 RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
 NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("leaf_off", "<u4"), ("root", "<u4")])
@@ -210,6 +239,9 @@ def lib(path=None):
                 "cda_share_proofs_validate": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32, P]),
                 "cda_share_proofs_validate_device": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32, P,
                                                              P]),
+                "cda_square_prove_namespace": (I32, [P, U32, P, U32, P, P, P, P, U64, P]),
+                "cda_nmt_verify_namespace": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, U32, P]),
+                "cda_nmt_verify_namespace_device": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, U32, P, P]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -602,6 +634,36 @@ class Context:
                                                       V(stream or 0))
         _check(rc, ctx=self)
 
+    def nmt_verify_namespace(self, descs, namespaces, roots, nodes, leaf_hashes, leaves):
+        """cda_nmt_verify_namespace: nmt Proof.VerifyNamespace of a batch.  descs: NMT_NS_PROOF_DESC_DTYPE rows;
+        namespaces (nproofs, 29); roots (nroots, 90); nodes (nnodes, 90); leaf_hashes (n, 90); leaves (nleaves, 512), all
+        uint8.  -> verdicts (nproofs,) uint8, 1 = verifies."""
+        descs = np.ascontiguousarray(descs, NMT_NS_PROOF_DESC_DTYPE)
+        n = len(descs)
+        namespaces = np.ascontiguousarray(namespaces, np.uint8).reshape(n, NAMESPACE_SIZE)
+        roots = np.ascontiguousarray(roots, np.uint8).reshape(-1, NODE_SIZE)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        leaf_hashes = np.ascontiguousarray(leaf_hashes, np.uint8).reshape(-1, NODE_SIZE)
+        leaves = np.ascontiguousarray(leaves, np.uint8).reshape(-1, SHARE_SIZE)
+        ok = np.zeros(n, np.uint8)
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_nmt_verify_namespace(self._h, n, _p(descs), _p(namespaces), p(roots), len(roots), p(nodes),
+                                              len(nodes), p(leaf_hashes), len(leaf_hashes), p(leaves), len(leaves),
+                                              _p(ok))
+        _check(rc, ctx=self)
+        return ok
+
+    def nmt_verify_namespace_device(self, nproofs, d_descs, d_namespaces, d_roots, nroots, d_nodes, nnodes,
+                                    d_leaf_hashes, nleaf_hashes, d_leaves, nleaves, d_ok, stream=None):
+        """cda_nmt_verify_namespace_device: the same with device addresses, asynchronous on `stream`."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_nmt_verify_namespace_device(self._h, nproofs, V(d_descs), V(d_namespaces), V(d_roots), nroots,
+                                                     V(d_nodes), nnodes, V(d_leaf_hashes), nleaf_hashes, V(d_leaves),
+                                                     nleaves, V(d_ok), V(stream or 0))
+        _check(rc, ctx=self)
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -729,6 +791,53 @@ class Square:
                                     for r in range(lo, hi)], int(rows[lo]["row"]), int(rows[hi - 1]["row"]))
             out.append(P.ShareProof(data, nmt, ns[1:], row_proof, ns[0], raw["data_root"]))
         return out
+
+    @staticmethod
+    def namespace_queries(queries):
+        """(axis, index, namespace) tuples -> NAMESPACE_QUERY_DTYPE rows (rows of that dtype pass through)."""
+        if isinstance(queries, np.ndarray) and queries.dtype == NAMESPACE_QUERY_DTYPE:
+            return np.ascontiguousarray(queries)
+        q = np.zeros(len(queries), NAMESPACE_QUERY_DTYPE)
+        for i, (axis, index, ns) in enumerate(queries):
+            ns = bytes(ns)
+            if len(ns) != NAMESPACE_SIZE:
+                raise ValueError(f"namespace of {len(ns)} bytes: cda_square_prove_namespace takes {NAMESPACE_SIZE}")
+            q[i] = (axis, index, np.frombuffer(ns, np.uint8), 0)
+        return q
+
+    def prove_namespace(self, queries, want_shares=True, shares_cap=None):
+        """cda_square_prove_namespace: nmt ProveNamespace of many (axis, index, namespace) queries, one call.
+        -> (results (nq,) NAMESPACE_RESULT_DTYPE, nodes (nq, max_nodes, 90), leaf_hashes (nq, 90), shares (n, 512) or
+        None): query q's proof is nodes[q, :results[q]["nnodes"]], its shares are
+        shares[share_off : share_off + nshares].  shares_cap: bytes of the share buffer to offer (default: the bound
+        nq * 2k * 512 that always suffices, trimmed to the total afterwards)."""
+        q = self.namespace_queries(queries)
+        nq, mn, w = len(q), max(1, self.max_nodes), 2 * self.k
+        results = np.zeros(nq, NAMESPACE_RESULT_DTYPE)
+        nodes = np.zeros((nq, mn, NODE_SIZE), np.uint8)
+        leaf_hashes = np.zeros((nq, NODE_SIZE), np.uint8)
+        cap = nq * w * SHARE_SIZE if shares_cap is None else int(shares_cap)
+        shares = np.zeros((max(1, cap // SHARE_SIZE), SHARE_SIZE), np.uint8) if want_shares else None
+        total = ctypes.c_uint64(0)
+        rc = self._ctx._L.cda_square_prove_namespace(self._h, nq, _p(q), mn, _p(results), _p(nodes), _p(leaf_hashes),
+                                                     _p(shares), cap if want_shares else 0, ctypes.byref(total))
+        self.nshares_total = int(total.value)
+        _check(rc, ctx=self._ctx)
+        return results, nodes, leaf_hashes, (shares[:self.nshares_total] if want_shares else None)
+
+    def prove_namespace_device(self, queries, max_nodes, d_results, d_nodes, d_leaf_hashes, d_shares=0, shares_cap=0):
+        """cda_square_prove_namespace with the outputs at device addresses (queries stay host records).  -> the
+        number of shares of all results (also when the call fails for a shares_cap too small: CdaError E_ARG, the
+        total then in self.nshares_total)."""
+        q = self.namespace_queries(queries)
+        V = ctypes.c_void_p
+        total = ctypes.c_uint64(0)
+        rc = self._ctx._L.cda_square_prove_namespace(self._h, len(q), _p(q), max_nodes, V(d_results), V(d_nodes),
+                                                     V(d_leaf_hashes), V(d_shares or None), shares_cap,
+                                                     ctypes.byref(total))
+        self.nshares_total = int(total.value)
+        _check(rc, ctx=self._ctx)
+        return self.nshares_total
 
     def close(self):
         if getattr(self, "_h", None):

@@ -96,6 +96,89 @@ class NMTProof:
             h = node(h, nodes.pop(0))
         return not state["bad"] and h == bytes(root)
 
+    def is_empty(self):
+        """nmt Proof.IsEmptyProof: an empty range and no nodes."""
+        return self.start == self.end and not self.nodes and not self.leaf_hash
+
+    def is_of_absence(self):
+        """nmt Proof.IsOfAbsence: the proof carries the node of the leaf after the absent namespace."""
+        return bool(self.leaf_hash)
+
+    def verify_namespace(self, nid, leaves, root):
+        """nmt Proof.VerifyNamespace(sha256, nid, leavesWithoutNamespace, root) with IgnoreMaxNamespace(true): the
+        leaves are ALL the leaves of namespace nid under root, in order (rules V1-V6).
+          - root, nodes and leaf_hash must have min <= max;
+          - an empty range verifies iff there are no nodes, no leaf_hash and no leaves, and nid lies outside the root's
+            [min, max] (or the root is the empty tree's);
+          - with a leaf_hash (absence) the range is one leaf whose node is leaf_hash, nid < leaf_hash.min, and the
+            leaves are ignored; without one each leaf hashes as nid ‖ nid ‖ SHA256(0x00 ‖ nid ‖ leaf);
+          - completeness: every subtree the proof gives left of the range has max < nid, every one right of it (those
+            applied above the recomputed subtree included) has min > nid;
+          - the root recomputed as verify_inclusion does must equal root.
+        The recursion classifies a popped node by where its subtree lies, not by its position in the list."""
+        nid = bytes(nid)
+        n = len(nid)
+        size = 2 * n + 32
+        root, leaf_hash = bytes(root), bytes(self.leaf_hash or b"")
+        nodes = [bytes(x) for x in self.nodes]
+        if len(root) != size or any(len(x) != size for x in nodes) or (leaf_hash and len(leaf_hash) != size):
+            return False
+        if any(x[:n] > x[n:2 * n] for x in nodes + [root] + ([leaf_hash] if leaf_hash else [])):
+            return False
+        if self.start < 0 or self.start > self.end:
+            return False
+        if self.start == self.end:
+            if nodes or leaf_hash or leaves:
+                return False
+            return nid < root[:n] or nid > root[n:2 * n] or root == bytes(2 * n) + _sha256(b"")
+        if leaf_hash:
+            if self.end != self.start + 1 or not nid < leaf_hash[:n]:
+                return False
+            hashes = [leaf_hash]
+        else:
+            if len(leaves) != self.end - self.start:
+                return False
+            hashes = [nid + nid + _sha256(b"\x00", nid, bytes(leaf)) for leaf in leaves]
+        parity = b"\xff" * n
+        state = {"bad": False}
+
+        def node(left, right):
+            if left[n:2 * n] > right[:n]:
+                state["bad"] = True
+            mx = left[n:2 * n] if right[:n] == parity else right[n:2 * n]
+            return left[:n] + mx + _sha256(b"\x01", left, right)
+
+        def pop(on_left):
+            if not nodes:
+                return None
+            x = nodes.pop(0)
+            if (x[n:2 * n] >= nid) if on_left else (x[:n] <= nid):
+                state["bad"] = True  # a subtree outside the range that may hold leaves of nid
+            return x
+
+        def compute(lo, hi):
+            if hi <= self.start:
+                return pop(True)
+            if lo >= self.end:
+                return pop(False)
+            if hi - lo == 1:
+                return hashes.pop(0) if hashes else None
+            k = _split_point(hi - lo)
+            left, right = compute(lo, lo + k), compute(lo + k, hi)
+            if right is None:
+                return left
+            if left is None:
+                state["bad"] = True
+                return None
+            return node(left, right)
+
+        h = compute(0, max(1, _split_point(self.end) * 2))
+        if h is None or hashes:
+            return False
+        while nodes:
+            h = node(h, pop(False))
+        return not state["bad"] and h == root
+
 
 @dataclass
 class Proof:

@@ -91,6 +91,44 @@ class ErasuredNamespacedMerkleTree:
         rec(0, max(1, _split_point(n) * 2), True)
         return NMTProof(start, end, nodes)
 
+    def _root_node(self):
+        """The tree's root node on the host (hashlib), IgnoreMaxNamespace(true); the empty tree's for no leaves."""
+        from .proof import _split_point
+        leaves = self._leaf_nodes()
+        if not leaves:
+            return bytes(2 * NAMESPACE_SIZE) + hashlib.sha256(b"").digest()
+
+        def rec(lo, hi):
+            if hi - lo == 1:
+                return leaves[lo]
+            k = _split_point(hi - lo)
+            left, right = rec(lo, lo + k), rec(lo + k, hi)
+            mx = left[NAMESPACE_SIZE:2 * NAMESPACE_SIZE] if right[:NAMESPACE_SIZE] == PARITY_SHARES_NAMESPACE else \
+                right[NAMESPACE_SIZE:2 * NAMESPACE_SIZE]
+            return left[:NAMESPACE_SIZE] + mx + hashlib.sha256(b"\x01" + left + right).digest()
+        return rec(0, len(leaves))
+
+    def prove_namespace(self, nid):
+        """nmt Tree.ProveNamespace(nid) on the erasured tree (rules P1-P3) -> cda.proof.NMTProof:
+          - nid outside the root's [min, max]: the empty proof (start = end = 0, no nodes);
+          - nid present: the inclusion proof of its whole run of leaves [start, end);
+          - nid inside the root's range but absent: the proof of the first leaf with a larger namespace, with
+            leaf_hash = that leaf's node.
+        The leaves of the run are self._leaves[start:end] (is_of_absence() / is_empty(): none)."""
+        from .proof import NMTProof
+        nid = bytes(nid)
+        root = self._root_node()
+        if not self._leaves or nid < root[:NAMESPACE_SIZE] or nid > root[NAMESPACE_SIZE:2 * NAMESPACE_SIZE]:
+            return NMTProof(0, 0, [])
+        leaf_nodes = self._leaf_nodes()
+        start = sum(1 for x in leaf_nodes if x[:NAMESPACE_SIZE] < nid)
+        end = sum(1 for x in leaf_nodes if x[:NAMESPACE_SIZE] <= nid)
+        if start < end:
+            return self.prove_range(start, end)
+        p = self.prove_range(start, start + 1)
+        p.leaf_hash = leaf_nodes[start]
+        return p
+
 
 def new_erasured_namespaced_merkle_tree(square_size, axis_index, ctx=None):
     return ErasuredNamespacedMerkleTree(square_size, axis_index, ctx)

@@ -2,6 +2,7 @@
 #include "plan.h"
 
 #include "merkle_walk_rule.h"
+#include "nmt_namespace_rule.h"
 #include "nmt_verify_rule.h"
 
 #include <string.h>
@@ -233,6 +234,24 @@ bool merkle_walk(int64_t total, int64_t index, uint64_t naunts, std::vector<uint
   if (!w.init(total, index, naunts)) return false;
   for (int j = 0; j < w.depth; j++) aunt_on_left.push_back(w.aunt_on_left(j) ? 1 : 0);
   return true;
+}
+
+NamespaceBounds namespace_bounds(const uint8_t* leaf_ns, size_t stride, uint32_t nleaves, const uint8_t* root,
+                                 const uint8_t* nid) {
+  if (ns_outside_root(nid, root)) return NamespaceBounds{CDA_NSP_EMPTY, 0, 0};  // P1
+  uint32_t below = 0, upto = 0;  // the leaves are sorted: the counts are the bounds
+  for (uint32_t i = 0; i < nleaves; i++) {
+    const int c = ns_compare(leaf_ns + (size_t)i * stride, nid);
+    below += c < 0;
+    upto += c <= 0;
+  }
+  if (below < upto) return NamespaceBounds{CDA_NSP_INCLUSION, below, upto};  // P2
+  return NamespaceBounds{CDA_NSP_ABSENCE, below, below + 1};                   // P3
+}
+
+int namespace_precheck(const uint8_t* nid, uint32_t start, uint32_t end, const uint8_t* nodes, uint32_t nnodes,
+                       const uint8_t* leaf_hash, uint32_t nleaves, const uint8_t* root) {
+  return (int)ns_precheck(nid, start, end, nodes, nnodes, leaf_hash, nleaves, root);
 }
 
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len) {

@@ -8,6 +8,9 @@
 //   prove_range              nmt buildRangeProof on a perfect tree (inclusion.cpp, cda_share_inclusion_proof)
 //   verify_walk              nmt Proof.VerifyInclusion's node schedule (nmt_verify_rule.h: what the kernels of
 //                            cda_nmt_verify evaluate per proof)
+//   namespace_bounds,        nmt ProveNamespace's bounds and Proof.VerifyNamespace's checks before hashing
+//   namespace_precheck       (nmt_namespace_rule.h: what the kernels of cda_square_prove_namespace and
+//                            cda_nmt_verify_namespace evaluate)
 //   check_square_plan        the share-layout plan of cda_build_ods_device (square.cpp)
 #pragma once
 #include <stddef.h>
@@ -110,6 +113,21 @@ bool verify_walk(uint32_t s, uint32_t e, uint32_t nnodes, std::vector<VerifyStep
 // go-square merkle Proof.Verify's path for (total, index) with naunts aunts (merkle_walk_rule.h): aunt_on_left[j] says
 // on which side aunt j is hashed, bottom-up.  False: the proof is rejected by its numbers alone.
 bool merkle_walk(int64_t total, int64_t index, uint64_t naunts, std::vector<uint8_t>& aunt_on_left);
+
+// nmt ProveNamespace's bounds (nmt_namespace_rule.h, P1-P3) over the namespaces of a tree's leaves in order (leaf i's
+// at leaf_ns + i * stride, 29 B) and its root node (90 B): kind CDA_NSP_*; EMPTY: start = end = 0; INCLUSION: the
+// namespace's run [start, end); ABSENCE: [start, start + 1), the first leaf with a larger namespace.
+struct NamespaceBounds {
+  uint32_t kind, start, end;
+};
+NamespaceBounds namespace_bounds(const uint8_t* leaf_ns, size_t stride, uint32_t nleaves, const uint8_t* root,
+                                 const uint8_t* nid);
+// nmt Proof.VerifyNamespace's checks before any hashing (nmt_namespace_rule.h, V1-V5: what the prep kernel of
+// cda_nmt_verify_namespace evaluates per proof).  nodes: nnodes packed 90-B nodes; leaf_hash: 90 B or null.
+// 0: false; 1: true (an empty proof); 2: true iff VerifyInclusion's recomputation from the leaves gives the root;
+// 3: true iff the recomputation from leaf_hash as leaf `start` gives the root.
+int namespace_precheck(const uint8_t* nid, uint32_t start, uint32_t end, const uint8_t* nodes, uint32_t nnodes,
+                       const uint8_t* leaf_hash, uint32_t nleaves, const uint8_t* root);
 
 // shares a sequence of `len` bytes needs (compact: 474 / 478 per share; sparse: 478 / 482; padding: 1)
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len);

@@ -10,6 +10,9 @@
 //   cda_square_share_proofs    pkg/proof NewShareInclusionProof (proof.go:55-167) for many share ranges per launch:
 //                              NMT range proofs, row roots and their RFC-6962 proofs in the data root
 //   cda_share_proofs_validate[_device]  ShareProof.Validate (share_proof.go:16-82, row_proof.go:13-48) of a batch
+//   cda_square_prove_namespace nmt ProveNamespace of any row or column tree: the namespace's shares with an inclusion
+//                              proof, or an absence or an empty proof, many queries per launch
+//   cda_nmt_verify_namespace[_device]   nmt Proof.VerifyNamespace (completeness included) of a batch
 // The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.
 //
 // Ownership: a square's device memory is one allocation of its own, so no other call on the context can touch it.
@@ -460,6 +463,165 @@ int cda_share_proofs_validate_device(cda_ctx* c, uint32_t nproofs, const void* d
   validate_workspace_bind(a, c->plan.p);
   ProfScope ps(c, "share_proofs_validate", dl.s);
   return launch_share_proofs_validate(a, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_square_prove_namespace(cda_square* sq, uint32_t nq, const cda_namespace_query* q, uint32_t max_nodes,
+                               cda_namespace_result* results, uint8_t* nodes, uint8_t* leaf_hashes,
+                               uint8_t* shares_or_null, uint64_t shares_cap, uint64_t* nshares_total) {
+  cda_ctx* c = sq ? sq->c : nullptr;
+  CDA_API_TRY
+  if (nshares_total) *nshares_total = 0;
+  if (!c || !nshares_total) return CDA_E_ARG;  // null, or a square whose context was freed
+  if (nq == 0) return CDA_OK;
+  if (!q || !results || !nodes || !leaf_hashes) return CDA_E_ARG;
+  if (nq > (1u << 24)) return CDA_E_UNSUPPORTED;
+  const uint32_t w = 2 * sq->k;
+  if (max_nodes < 2 * (uint32_t)sq->view.log2w) return CDA_E_ARG;
+  for (uint32_t i = 0; i < nq; i++)
+    if (q[i].axis > 1 || q[i].index >= w) return CDA_E_ARG;
+  if ((uint64_t)nq * w > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;  // share offsets are 32-bit
+  Lock l(c);
+  hipStream_t s = c->stream;
+  // staging in the context's workspace: queries | results | leaf hashes | the share total, the nodes, the shares
+  const size_t q_b = align256((size_t)nq * sizeof(cda_namespace_query));
+  const size_t res_b = align256((size_t)nq * sizeof(cda_namespace_result));
+  const size_t lh_b = align256((size_t)nq * CDA_NODE_SIZE), nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE;
+  int rc;
+  if ((rc = ensure(c, c->plan, q_b + res_b + lh_b + 256)) || (rc = ensure(c, c->nodes, nodes_b))) return rc;
+  uint8_t* base = (uint8_t*)c->plan.p;
+  cda_namespace_query* d_q = (cda_namespace_query*)base;
+  cda_namespace_result* d_res = (cda_namespace_result*)(base + q_b);
+  uint8_t* d_lh = base + q_b + res_b;
+  unsigned long long* d_total = (unsigned long long*)(d_lh + lh_b);
+  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_namespace_query), hipMemcpyHostToDevice, s), "H2D"))
+    return CDA_E_DEVICE;
+  {
+    ProfScope ps(c, "square_prove_namespace", s);
+    if (launch_square_prove_namespace(sq->view, d_q, nq, max_nodes, d_res, (uint8_t*)c->nodes.p, d_lh, d_total, s))
+      return CDA_E_DEVICE;
+  }
+  // How many shares the namespaces hold is the data's to say: with the shares wanted the host waits here, once, for
+  // the total that sizes their staging; without them the total comes back with everything else.
+  unsigned long long total = 0;
+  if (!dev_ok(c, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s), "D2H")) return CDA_E_DEVICE;
+  bool fits = true;
+  size_t shares_b = 0;
+  if (shares_or_null) {
+    if (!dev_ok(c, hipStreamSynchronize(s), "sync")) return CDA_E_DEVICE;
+    *nshares_total = total;
+    fits = total * CDA_SHARE <= shares_cap;
+    shares_b = fits ? (size_t)total * CDA_SHARE : 0;
+    if (shares_b) {
+      if ((rc = ensure(c, c->payload, shares_b))) return rc;
+      ProfScope ps(c, "namespace_shares", s);
+      if (launch_namespace_shares(sq->view, d_q, nq, d_res, (uint8_t*)c->payload.p, s)) return CDA_E_DEVICE;
+    }
+  }
+  if (!copy_any(c, results, d_res, (size_t)nq * sizeof(cda_namespace_result), s) ||
+      !copy_any(c, nodes, c->nodes.p, nodes_b, s) || !copy_any(c, leaf_hashes, d_lh, (size_t)nq * CDA_NODE_SIZE, s) ||
+      !copy_any(c, shares_or_null, c->payload.p, shares_b, s) || !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  *nshares_total = total;
+  flush_profile(c);
+  return fits ? CDA_OK : CDA_E_ARG;
+  CDA_API_CATCH(c)
+}
+
+int cda_nmt_verify_namespace(cda_ctx* c, uint32_t nproofs, const cda_nmt_ns_proof_desc* descs,
+                             const uint8_t* namespaces, const uint8_t* roots, uint32_t nroots, const uint8_t* nodes,
+                             uint32_t nnodes_total, const uint8_t* leaf_hashes, uint32_t nleaf_hashes,
+                             const uint8_t* leaves, uint32_t nleaves_total, uint8_t* ok) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!descs || !namespaces || !ok || (nroots && !roots) || (nnodes_total && !nodes) ||
+      (nleaf_hashes && !leaf_hashes) || (nleaves_total && !leaves))
+    return CDA_E_ARG;
+  for (uint32_t i = 0; i < nproofs; i++)
+    if (descs[i].end > kVerifyMaxEnd) return CDA_E_ARG;
+  Lock l(c);
+  hipStream_t s = c->stream;
+  // descriptors | namespaces | verdicts | roots | leaf hashes | the kernels' workspace, the nodes, the leaves
+  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_nmt_ns_proof_desc));
+  const size_t ns_b = align256((size_t)nproofs * CDA_NAMESPACE_SIZE), ok_b = align256(nproofs);
+  const size_t roots_b = (size_t)nroots * CDA_NODE_SIZE, lh_b = (size_t)nleaf_hashes * CDA_NODE_SIZE;
+  const size_t nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE, leaves_b = (size_t)nleaves_total * CDA_SHARE;
+  int rc;
+  if ((rc = ensure(c, c->plan,
+                   desc_b + ns_b + ok_b + align256(roots_b) + align256(lh_b) + ns_verify_workspace_bytes(nproofs))) ||
+      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
+    return rc;
+  uint8_t* base = (uint8_t*)c->plan.p;
+  uint8_t* d_roots = base + desc_b + ns_b + ok_b;
+  uint8_t* d_lh = d_roots + align256(roots_b);
+  NsVerifyArgs a{};
+  a.descs = (const cda_nmt_ns_proof_desc*)base;
+  a.namespaces = base + desc_b;
+  a.ok = base + desc_b + ns_b;
+  a.roots = d_roots;
+  a.leaf_hashes = d_lh;
+  a.nodes = (const uint8_t*)c->nodes.p;
+  a.leaves = (const uint8_t*)c->payload.p;
+  a.nproofs = nproofs;
+  a.nroots = nroots;
+  a.nnodes_total = nnodes_total;
+  a.nleaf_hashes = nleaf_hashes;
+  a.nleaves_total = nleaves_total;
+  ns_verify_workspace_bind(a, d_lh + align256(lh_b));
+  if (!dev_ok(c, hipMemcpyAsync(base, descs, (size_t)nproofs * sizeof(cda_nmt_ns_proof_desc), hipMemcpyHostToDevice, s),
+              "H2D") ||
+      !dev_ok(c, hipMemcpyAsync(base + desc_b, namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE,
+                                hipMemcpyHostToDevice, s), "H2D") ||
+      (roots_b && !dev_ok(c, hipMemcpyAsync(d_roots, roots, roots_b, hipMemcpyHostToDevice, s), "H2D")) ||
+      (lh_b && !dev_ok(c, hipMemcpyAsync(d_lh, leaf_hashes, lh_b, hipMemcpyHostToDevice, s), "H2D")))
+    return CDA_E_DEVICE;
+  if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
+  if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
+  {
+    ProfScope ps(c, "nmt_verify_namespace", s);
+    if (launch_nmt_verify_namespace(a, s)) return CDA_E_DEVICE;
+  }
+  if (!dev_ok(c, hipMemcpyAsync(ok, a.ok, nproofs, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+  CDA_API_CATCH(c)
+}
+
+int cda_nmt_verify_namespace_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
+                                    const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
+                                    const void* d_leaf_hashes, uint32_t nleaf_hashes, const void* d_leaves,
+                                    uint32_t nleaves_total, void* d_ok, void* stream) {
+  CDA_API_TRY
+  if (!c) return CDA_E_ARG;
+  if (nproofs == 0) return CDA_OK;
+  if (!d_descs || !d_namespaces || !d_ok || (nroots && !d_roots) || (nnodes_total && !d_nodes) ||
+      (nleaf_hashes && !d_leaf_hashes) || (nleaves_total && !d_leaves))
+    return CDA_E_ARG;
+  // the kernels read shares 16 bytes and nodes, roots, leaf hashes and descriptors 4 bytes at a time
+  if (((uintptr_t)d_leaves & 15) ||
+      (((uintptr_t)d_nodes | (uintptr_t)d_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_descs) & 3))
+    return CDA_E_ARG;
+  NsVerifyArgs a{};
+  a.descs = (const cda_nmt_ns_proof_desc*)d_descs;
+  a.namespaces = (const uint8_t*)d_namespaces;
+  a.roots = (const uint8_t*)d_roots;
+  a.nodes = (const uint8_t*)d_nodes;
+  a.leaf_hashes = (const uint8_t*)d_leaf_hashes;
+  a.leaves = (const uint8_t*)d_leaves;
+  a.ok = (uint8_t*)d_ok;
+  a.nproofs = nproofs;
+  a.nroots = nroots;
+  a.nnodes_total = nnodes_total;
+  a.nleaf_hashes = nleaf_hashes;
+  a.nleaves_total = nleaves_total;
+  DevLock dl(c, (hipStream_t)stream);
+  if (int rc = ensure(c, c->plan, ns_verify_workspace_bytes(nproofs))) return rc;
+  ns_verify_workspace_bind(a, c->plan.p);
+  ProfScope ps(c, "nmt_verify_namespace", dl.s);
+  return launch_nmt_verify_namespace(a, dl.s) ? CDA_E_DEVICE : CDA_OK;
   CDA_API_CATCH(c)
 }
 

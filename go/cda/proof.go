@@ -376,3 +376,163 @@ func ValidateShareProofs(ctx *Context, proofs []SquareShareProof, namespaces [][
 	}
 	return verdicts, nil
 }
+
+// NamespaceProofKind says what ProveNamespace found in a tree (the CDA_NSP_* codes of cda.h).
+type NamespaceProofKind uint32
+
+const (
+	// NamespaceEmpty: the namespace lies outside the tree root's [min, max]; the proof has no nodes.
+	NamespaceEmpty NamespaceProofKind = 0
+	// NamespaceInclusion: Shares are all the tree's leaves of the namespace, [Start, End) their range.
+	NamespaceInclusion NamespaceProofKind = 1
+	// NamespaceAbsence: inside the root's range but not present; LeafHash is the node of the first leaf with a
+	// larger namespace, [Start, Start+1) its range.
+	NamespaceAbsence NamespaceProofKind = 2
+)
+
+// NamespaceQuery asks tree (Axis, Index) of the extended square for everything of a 29-byte namespace.
+type NamespaceQuery struct {
+	Axis, Index int
+	Namespace   []byte
+}
+
+// NamespaceProof is nmt's ProveNamespace result for one tree: the namespace's shares (inclusion only) and the proof
+// that they are all of them (proof.pb.go NMTProof: Start, End, Nodes, LeafHash).
+type NamespaceProof struct {
+	Kind       NamespaceProofKind
+	Start, End int
+	Nodes      [][]byte // left to right
+	LeafHash   []byte   // nil unless Kind == NamespaceAbsence
+	Shares     [][]byte
+}
+
+// ProveNamespace is nmt's Tree.ProveNamespace for every query from ONE call (cda_square_prove_namespace): the
+// namespace's run is found in the retained leaf records on the device, the nodes are gathered from the retained
+// trees, the shares copied from the retained EDS.
+func (sq *RetainedSquare) ProveNamespace(queries []NamespaceQuery) ([]NamespaceProof, error) {
+	if sq.h == nil {
+		return nil, fmt.Errorf("cda: square is closed")
+	}
+	if len(queries) == 0 {
+		return nil, nil
+	}
+	w := 2 * sq.K
+	lg := 0
+	for 1<<lg < w {
+		lg++
+	}
+	maxNodes := 2 * lg
+	q := make([]C.cda_namespace_query, len(queries))
+	for i, x := range queries {
+		if x.Axis < 0 || x.Axis > 1 || x.Index < 0 || x.Index >= w || len(x.Namespace) != NamespaceSize {
+			return nil, fmt.Errorf("cda: namespace query %d: axis %d, index %d, namespace of %d bytes", i, x.Axis,
+				x.Index, len(x.Namespace))
+		}
+		q[i].axis, q[i].index = C.uint32_t(x.Axis), C.uint32_t(x.Index)
+		for j := 0; j < NamespaceSize; j++ {
+			q[i].ns[j] = C.uint8_t(x.Namespace[j])
+		}
+	}
+	res := make([]C.cda_namespace_result, len(q))
+	nodes := make([]byte, len(q)*maxNodes*NodeSize)
+	lh := make([]byte, len(q)*NodeSize)
+	// nq * 2k * 512 bytes always suffice; ask for the proofs first and size the share buffer from the total
+	var total C.uint64_t
+	rc := C.cda_square_prove_namespace(sq.h, C.uint32_t(len(q)), &q[0], C.uint32_t(maxNodes), &res[0], ptr(nodes),
+		ptr(lh), nil, 0, &total)
+	if rc != 0 {
+		return nil, toErr(rc, nil)
+	}
+	var shares []byte
+	if total > 0 {
+		shares = make([]byte, int(total)*ShareSize)
+		rc = C.cda_square_prove_namespace(sq.h, C.uint32_t(len(q)), &q[0], C.uint32_t(maxNodes), &res[0], ptr(nodes),
+			ptr(lh), ptr(shares), C.uint64_t(len(shares)), &total)
+		if rc != 0 {
+			return nil, toErr(rc, nil)
+		}
+	}
+	out := make([]NamespaceProof, len(q))
+	for i := range out {
+		r := &res[i]
+		p := &out[i]
+		p.Kind, p.Start, p.End = NamespaceProofKind(r.kind), int(r.start), int(r.end)
+		for j := 0; j < int(r.nnodes); j++ {
+			o := (i*maxNodes + j) * NodeSize
+			p.Nodes = append(p.Nodes, nodes[o:o+NodeSize:o+NodeSize])
+		}
+		if p.Kind == NamespaceAbsence {
+			p.LeafHash = lh[i*NodeSize : (i+1)*NodeSize : (i+1)*NodeSize]
+		}
+		if n := int(r.nshares); n > 0 {
+			o := int(r.share_off) * ShareSize
+			p.Shares = split(shares[o:o+n*ShareSize], n)
+		}
+	}
+	return out, nil
+}
+
+// VerifyNamespace is nmt's Proof.VerifyNamespace of a batch on the GPU (cda_nmt_verify_namespace): proof i claims
+// that proofs[i].Shares are ALL the leaves of namespaces[i] in the tree with root roots[i] (90 bytes).  Completeness
+// is part of the verdict: an inclusion proof of a part of the namespace's run is false.  A false proof is a verdict,
+// never an error.
+func VerifyNamespace(ctx *Context, proofs []NamespaceProof, namespaces [][]byte, roots [][]byte) ([]bool, error) {
+	if len(proofs) == 0 {
+		return nil, nil
+	}
+	if len(namespaces) != len(proofs) || len(roots) != len(proofs) {
+		return nil, fmt.Errorf("cda: %d proofs, %d namespaces, %d roots", len(proofs), len(namespaces), len(roots))
+	}
+	descs := make([]C.cda_nmt_ns_proof_desc, len(proofs))
+	var ns, rr, nodes, lhs, leaves []byte
+	nnodes, nlh, nleaves := 0, 0, 0
+	for i := range proofs {
+		p := &proofs[i]
+		if len(namespaces[i]) != NamespaceSize || len(roots[i]) != NodeSize || p.Start < 0 || p.End < 0 {
+			return nil, fmt.Errorf("cda: proof %d: namespace of %d bytes, root of %d, range [%d, %d)", i,
+				len(namespaces[i]), len(roots[i]), p.Start, p.End)
+		}
+		d := &descs[i]
+		d.start, d.end = C.uint32_t(p.Start), C.uint32_t(p.End)
+		d.node_off, d.nnodes = C.uint32_t(nnodes), C.uint32_t(len(p.Nodes))
+		d.leaf_off, d.nleaves = C.uint32_t(nleaves), C.uint32_t(len(p.Shares))
+		d.root = C.uint32_t(i)
+		d.leaf_hash = C.CDA_NO_LEAF_HASH
+		if len(p.LeafHash) != 0 {
+			if len(p.LeafHash) != NodeSize {
+				return nil, fmt.Errorf("cda: proof %d: leaf hash of %d bytes", i, len(p.LeafHash))
+			}
+			d.leaf_hash = C.uint32_t(nlh)
+			lhs = append(lhs, p.LeafHash...)
+			nlh++
+		}
+		ns = append(ns, namespaces[i]...)
+		rr = append(rr, roots[i]...)
+		for _, x := range p.Nodes {
+			if len(x) != NodeSize {
+				return nil, fmt.Errorf("cda: proof %d: node of %d bytes", i, len(x))
+			}
+			nodes = append(nodes, x...)
+		}
+		for _, s := range p.Shares {
+			if len(s) != ShareSize {
+				return nil, fmt.Errorf("cda: proof %d: share of %d bytes", i, len(s))
+			}
+			leaves = append(leaves, s...)
+		}
+		nnodes += len(p.Nodes)
+		nleaves += len(p.Shares)
+	}
+	ok := make([]byte, len(proofs))
+	rc := C.cda_nmt_verify_namespace(ctx.c, C.uint32_t(len(descs)), &descs[0], ptr(ns), ptr(rr),
+		C.uint32_t(len(proofs)), ptr(nodes), C.uint32_t(nnodes), ptr(lhs), C.uint32_t(nlh), ptr(leaves),
+		C.uint32_t(nleaves), ptr(ok))
+	if rc != 0 {
+		return nil, toErr(rc, nil)
+	}
+	out := make([]bool, len(ok))
+	for i, v := range ok {
+		out[i] = v == 1
+	}
+	return out, nil
+}

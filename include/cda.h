@@ -421,6 +421,65 @@ int cda_share_proofs_validate_device(cda_ctx* ctx, uint32_t nproofs, const void*
                                      const void* d_leaves, uint32_t nleaves, const void* d_data_roots,
                                      uint32_t nroots, void* d_verdicts, void* stream);
 
+/* ---- namespace data with completeness proofs: nmt ProveNamespace / Proof.VerifyNamespace, batched ---- */
+/* "Everything of namespace ns in tree (axis, index), and a proof that nothing was withheld."  Namespaces compare as
+ * 29-byte big-endian strings; leaf i's namespace is the share's own in Q0 and 0xFF x 29 elsewhere. */
+typedef struct {
+  uint32_t axis, index;
+  uint8_t ns[29];
+  uint8_t pad_[3];
+} cda_namespace_query;
+enum { CDA_NSP_EMPTY = 0, CDA_NSP_INCLUSION = 1, CDA_NSP_ABSENCE = 2 };
+/* EMPTY (ns outside the root's [min, max]): start = end = 0, no nodes.  INCLUSION: [start, end) is the namespace's
+ * run of leaves, nodes = ProveRange(start, end), the run's cells are shares[share_off, share_off + nshares).
+ * ABSENCE (inside the root's range, not present): [start, start + 1) is the first leaf with a larger namespace, nodes
+ * = ProveRange(start, start + 1), leaf_hashes[q] is that leaf's 90-B node (NMTProof.leaf_hash), no shares. */
+typedef struct {
+  uint32_t kind, start, end, nnodes, share_off, nshares;
+} cda_namespace_result;
+/* nq queries of a retained square in one call.  results: nq records; nodes: nq x max_nodes x 90 B (query q's from
+ * slot q * max_nodes, unused slots zero); leaf_hashes: nq x 90 B (zero unless ABSENCE); shares_or_null: the shares of
+ * the INCLUSION results packed in query order, share_off[q] = the shares of the queries before q.  The share count
+ * depends on the data: *nshares_total (host memory) is always written; if shares_or_null is non-null and shares_cap
+ * (bytes) is too small the shares are not written, everything else is, and the call returns CDA_E_ARG (nq x 2k x 512
+ * bytes always suffice).  CDA_E_ARG before any launch for axis > 1, index >= 2k, max_nodes < 2 log2(2k) or a
+ * detached handle.  q is host memory; results, nodes, leaf_hashes and shares_or_null may each be host or device
+ * memory. */
+int cda_square_prove_namespace(cda_square* sq, uint32_t nq, const cda_namespace_query* q, uint32_t max_nodes,
+                               cda_namespace_result* results, uint8_t* nodes, uint8_t* leaf_hashes,
+                               uint8_t* shares_or_null, uint64_t shares_cap, uint64_t* nshares_total);
+
+#define CDA_NO_LEAF_HASH 0xFFFFFFFFu
+/* One proof of a cda_nmt_verify_namespace batch: nodes = nodes[node_off, node_off + nnodes) of 90 B, leaves =
+ * leaves[leaf_off, leaf_off + nleaves) of 512 B, root = roots[root] of 90 B, leaf_hash = leaf_hashes[leaf_hash] of
+ * 90 B or CDA_NO_LEAF_HASH; the namespace is namespaces[29p, 29p + 29). */
+typedef struct {
+  uint32_t start, end, node_off, nnodes, leaf_off, nleaves, root, leaf_hash;
+} cda_nmt_ns_proof_desc;
+/* Batched nmt Proof.VerifyNamespace (IgnoreMaxNamespace): ok[p] = 1 iff
+ *   - root, every node and the leaf hash have min <= max;
+ *   - start == end: no nodes, no leaf hash, no leaves, and ns outside the root's [min, max] or the root is that of the
+ *     empty tree; start > end is false;
+ *   - with a leaf hash (absence; leaves are ignored): end == start + 1 and ns < leaf_hash.min, and the root is
+ *     recomputed from the leaf hash as leaf `start`;
+ *   - without one (inclusion): nleaves == end - start, leaves hashed under the supplied namespace as cda_nmt_verify;
+ *   - completeness: the first popcount(start) nodes have max < ns, every later node has min > ns;
+ *   - the recomputed root (cda_nmt_verify's rules) equals the root.
+ * A false proof is a verdict, never an error code.  A descriptor outside the totals gets 0 and is not read through.
+ * The arrays cda_square_prove_namespace writes are accepted as they lie (node_off = q x max_nodes, leaf_hash = q for
+ * ABSENCE, leaf_off = share_off).  CDA_E_ARG if a descriptor has end > 65536. */
+int cda_nmt_verify_namespace(cda_ctx* ctx, uint32_t nproofs, const cda_nmt_ns_proof_desc* descs,
+                             const uint8_t* namespaces, const uint8_t* roots, uint32_t nroots, const uint8_t* nodes,
+                             uint32_t nnodes_total, const uint8_t* leaf_hashes, uint32_t nleaf_hashes,
+                             const uint8_t* leaves, uint32_t nleaves_total, uint8_t* ok);
+/* The same with every pointer in device memory (d_leaves 16-byte, d_nodes / d_roots / d_leaf_hashes / d_descs 4-byte
+ * aligned, else CDA_E_ARG), asynchronous on `stream`; a descriptor with end > 65536 gets ok = 0.  Uses the context's
+ * workspace. */
+int cda_nmt_verify_namespace_device(cda_ctx* ctx, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
+                                    const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
+                                    const void* d_leaf_hashes, uint32_t nleaf_hashes, const void* d_leaves,
+                                    uint32_t nleaves_total, void* d_ok, void* stream);
+
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
  * host plans the layout -- which sequence or blob goes where, the PFB share indexes, the compact
