@@ -59,6 +59,7 @@ EXPORTS = [
     "cda_square_open", "cda_square_close", "cda_square_prove", "cda_nmt_verify", "cda_nmt_verify_device",
     "cda_square_share_proofs", "cda_share_proofs_validate", "cda_share_proofs_validate_device",
     "cda_square_prove_namespace", "cda_nmt_verify_namespace", "cda_nmt_verify_namespace_device",
+    "cda_square_open_eds", "cda_befp_validate", "cda_befp_validate_device",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -133,6 +134,20 @@ class NmtNsProofDesc(ctypes.Structure):
                 ("root", ctypes.c_uint32), ("leaf_hash", ctypes.c_uint32)]
 
 
+class BefpDesc(ctypes.Structure):
+    """cda_befp_desc: one bad-encoding fraud proof of a cda_befp_validate batch."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("entry_off", ctypes.c_uint32),
+                ("nshares", ctypes.c_uint32), ("root_off", ctypes.c_uint32)]
+
+
+class BefpEntry(ctypes.Structure):
+    """cda_befp_entry: one share of a bad-encoding fraud proof and where its NMT proof's nodes lie."""
+    _fields_ = [("pos", ctypes.c_uint32), ("node_off", ctypes.c_uint32), ("nnodes", ctypes.c_uint32)]
+
+
+# cda_befp_validate's verdicts (include/cda.h CDA_BEFP_*)
+BEFP_FRAUD, BEFP_NO_FRAUD, BEFP_MALFORMED, BEFP_TOO_FEW, BEFP_BAD_SHARE = 1, 0, -1, -2, -3
+
 # cda_namespace_result.kind (include/cda.h CDA_NSP_*), and "no leaf hash" of a cda_nmt_ns_proof_desc
 NSP_EMPTY, NSP_INCLUSION, NSP_ABSENCE = range(3)
 NO_LEAF_HASH = 0xFFFFFFFF
@@ -155,6 +170,9 @@ NAMESPACE_RESULT_DTYPE = np.dtype([("kind", "<u4"), ("start", "<u4"), ("end", "<
                                    ("share_off", "<u4"), ("nshares", "<u4")])
 NMT_NS_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                     ("leaf_off", "<u4"), ("nleaves", "<u4"), ("root", "<u4"), ("leaf_hash", "<u4")])
+BEFP_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("entry_off", "<u4"), ("nshares", "<u4"),
+                            ("root_off", "<u4")])
+BEFP_ENTRY_DTYPE = np.dtype([("pos", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4")])
 RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
 NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("leaf_off", "<u4"), ("root", "<u4")])
@@ -242,6 +260,9 @@ def lib(path=None):
                 "cda_square_prove_namespace": (I32, [P, U32, P, U32, P, P, P, P, U64, P]),
                 "cda_nmt_verify_namespace": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, U32, P]),
                 "cda_nmt_verify_namespace_device": (I32, [P, U32, P, P, P, U32, P, U32, P, U32, P, U32, P, P]),
+                "cda_square_open_eds": (I32, [P, U32, P, ctypes.POINTER(P), P, P, P, P]),
+                "cda_befp_validate": (I32, [P, U32, U32, P, P, U32, P, P, U32, P, U32, P]),
+                "cda_befp_validate_device": (I32, [P, U32, U32, P, P, U32, P, P, U32, P, U32, P, P]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -575,6 +596,11 @@ class Context:
         -> Square (row_roots, col_roots, dah as attributes); use as a context manager or call close()."""
         return Square(self, shares)
 
+    def open_square_eds(self, eds):
+        """cda_square_open_eds: retain the extended square `eds` ((2k)^2, 512) as it was committed -- nothing is
+        extended and the encoding is not checked.  -> Square, as open_square."""
+        return Square(self, eds, extended=True)
+
     def nmt_verify(self, descs, namespaces, roots, nodes, leaves):
         """cda_nmt_verify: nmt Proof.VerifyInclusion of a batch.  descs: NMT_PROOF_DESC_DTYPE rows; namespaces
         (nproofs, 29); roots (nroots, 90); nodes (nnodes, 90); leaves (nleaves, 512), all uint8.  -> verdicts (nproofs,)
@@ -664,6 +690,32 @@ class Context:
                                                      nleaves, V(d_ok), V(stream or 0))
         _check(rc, ctx=self)
 
+    def befp_validate(self, k, descs, entries, shares, nodes, roots):
+        """cda_befp_validate: Validate of a batch of bad-encoding fraud proofs of 2k x 2k squares.  descs:
+        BEFP_DESC_DTYPE rows; entries: BEFP_ENTRY_DTYPE rows with shares (nentries, 512); nodes (n, 90); roots (n, 90),
+        per block the 2k row roots then the 2k column roots, all uint8.  -> verdicts (nproofs,) int32, BEFP_* codes."""
+        descs = np.ascontiguousarray(descs, BEFP_DESC_DTYPE)
+        entries = np.ascontiguousarray(entries, BEFP_ENTRY_DTYPE)
+        shares = np.ascontiguousarray(shares, np.uint8).reshape(len(entries), SHARE_SIZE)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        roots = np.ascontiguousarray(roots, np.uint8).reshape(-1, NODE_SIZE)
+        verdicts = np.full(len(descs), BEFP_MALFORMED, np.int32)
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_befp_validate(self._h, k, len(descs), p(descs), p(entries), len(entries), p(shares), p(nodes),
+                                       len(nodes), p(roots), len(roots), _p(verdicts))
+        _check(rc, ctx=self)
+        return verdicts
+
+    def befp_validate_device(self, k, nproofs, d_descs, d_entries, nentries, d_shares, d_nodes, nnodes, d_roots, nroots,
+                             d_verdicts, stream=None):
+        """cda_befp_validate_device: the same with device addresses, asynchronous on `stream`."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_befp_validate_device(self._h, k, nproofs, V(d_descs), V(d_entries), nentries, V(d_shares),
+                                              V(d_nodes), nnodes, V(d_roots), nroots, V(d_verdicts), V(stream or 0))
+        _check(rc, ctx=self)
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -684,12 +736,17 @@ class Context:
 
 
 class Square:
-    """cda_square: one extended block retained on the device (Context.open_square)."""
+    """cda_square: one extended block retained on the device (Context.open_square: the k x k shares are extended;
+    Context.open_square_eds: `shares` is the (2k)^2 extended square, retained as given)."""
 
-    def __init__(self, ctx, shares):
+    def __init__(self, ctx, shares, extended=False):
         shares = np.ascontiguousarray(shares, np.uint8)
         count, L = shares.shape
         self.k = max(1, int(round(count ** 0.5)))
+        if extended:
+            self.k //= 2
+            if L != SHARE_SIZE or count != 4 * self.k * self.k or self.k == 0:
+                raise ValueError("open_square_eds takes the (2k)^2 cells of an extended square, 512 bytes each")
         w = 2 * self.k
         self.row_roots = np.empty((w, NODE_SIZE), np.uint8)
         self.col_roots = np.empty((w, NODE_SIZE), np.uint8)
@@ -697,8 +754,12 @@ class Square:
         self._ctx, self._h = ctx, None
         h = ctypes.c_void_p()
         err = ErrInfo()
-        rc = ctx._L.cda_square_open(ctx._h, count, L, _p(shares), ctypes.byref(h), _p(self.row_roots),
-                                    _p(self.col_roots), _p(dah), ctypes.byref(err))
+        if extended:
+            rc = ctx._L.cda_square_open_eds(ctx._h, self.k, _p(shares), ctypes.byref(h), _p(self.row_roots),
+                                            _p(self.col_roots), _p(dah), ctypes.byref(err))
+        else:
+            rc = ctx._L.cda_square_open(ctx._h, count, L, _p(shares), ctypes.byref(h), _p(self.row_roots),
+                                        _p(self.col_roots), _p(dah), ctypes.byref(err))
         _check(rc, err, ctx)
         self._h = h
         self.dah = dah.tobytes()

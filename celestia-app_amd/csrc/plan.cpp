@@ -1,6 +1,7 @@
 // plan.cpp — host-only planners (plan.h).  No HIP: built into libcda and, alone, under the CPU sanitizers.
 #include "plan.h"
 
+#include "befp_rule.h"
 #include "merkle_walk_rule.h"
 #include "nmt_namespace_rule.h"
 #include "nmt_verify_rule.h"
@@ -252,6 +253,33 @@ NamespaceBounds namespace_bounds(const uint8_t* leaf_ns, size_t stride, uint32_t
 int namespace_precheck(const uint8_t* nid, uint32_t start, uint32_t end, const uint8_t* nodes, uint32_t nnodes,
                        const uint8_t* leaf_hash, uint32_t nleaves, const uint8_t* root) {
   return (int)ns_precheck(nid, start, end, nodes, nnodes, leaf_hash, nleaves, root);
+}
+
+void befp_precheck(uint32_t k, uint32_t nproofs, const cda_befp_desc* descs, const cda_befp_entry* entries,
+                   uint32_t nentries, const uint8_t* shares, uint32_t nnodes_total, uint32_t nroots, BefpPlan& out) {
+  const BefpTotals t{k, nentries, nnodes_total, nroots};
+  const size_t w = 2 * (size_t)k, slots = (size_t)nproofs * w;
+  out.pre.assign(nproofs, CDA_BEFP_MALFORMED);
+  out.axis_index.assign(nproofs, 0);
+  out.descs.assign(slots, befp_empty_desc());
+  out.namespaces.assign(slots * kBefpNsSize, 0);
+  out.mask.assign(slots, 1);
+  for (uint32_t p = 0; p < nproofs; p++) {
+    const cda_befp_desc& d = descs[p];
+    const bool head = befp_head_ok(d, t);
+    bool ok = true;
+    for (uint32_t j = 0; head && ok && j < d.nshares; j++) ok = befp_entry_ok(d, entries, j, t);
+    if ((out.pre[p] = befp_pre_verdict(d, head, ok, t)) != kBefpPending) continue;
+    out.axis_index[p] = d.index;
+    memset(out.mask.data() + p * w, 0, w);
+    for (uint32_t j = 0; j < d.nshares; j++) {
+      const uint32_t e = d.entry_off + j;
+      out.descs[p * w + j] = befp_nmt_desc(d, entries[e], e, k);
+      befp_namespace(k, d.index, entries[e].pos, shares + (size_t)e * kBefpShare,
+                     out.namespaces.data() + (p * w + j) * kBefpNsSize);
+      out.mask[p * w + entries[e].pos] = 1;
+    }
+  }
 }
 
 uint64_t segment_shares_needed(uint32_t kind, uint64_t len) {

@@ -12,6 +12,8 @@
 //   namespace_precheck       (nmt_namespace_rule.h: what the kernels of cda_square_prove_namespace and
 //                            cda_nmt_verify_namespace evaluate)
 //   check_square_plan        the share-layout plan of cda_build_ods_device (square.cpp)
+//   befp_precheck            a bad-encoding fraud proof's checks before any hashing and what the legs after them
+//                            are given (befp_rule.h: what the prep kernel of cda_befp_validate evaluates)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -135,6 +137,19 @@ uint64_t segment_shares_needed(uint32_t kind, uint64_t len);
 // and fits its sequence.  CDA_OK, CDA_E_ARG or CDA_E_SHARE_VERSION.
 int check_square_plan(uint32_t k, uint32_t nseg, const cda_share_segment* segs, uint64_t data_len,
                       uint32_t nreserved);
+
+// cda_befp_validate's prep step (befp_rule.h, B1 and B2) over a whole call, in the layout of the kernels' workspace:
+// per proof pre (CDA_BEFP_MALFORMED, CDA_BEFP_TOO_FEW or 2 = B3 and B4 decide) and the tree's axis index; per proof and
+// slot j < 2k the NMT descriptor and namespace of its j-th entry (empty / zero for a rejected proof and past nshares)
+// and the decoder's present mask (all ones for a rejected proof).  shares: nentries x 512 B.
+struct BefpPlan {
+  std::vector<int32_t> pre;
+  std::vector<uint64_t> axis_index;
+  std::vector<cda_nmt_proof_desc> descs;
+  std::vector<uint8_t> namespaces, mask;
+};
+void befp_precheck(uint32_t k, uint32_t nproofs, const cda_befp_desc* descs, const cda_befp_entry* entries,
+                   uint32_t nentries, const uint8_t* shares, uint32_t nnodes_total, uint32_t nroots, BefpPlan& out);
 
 }  // namespace plan
 }  // namespace cda

@@ -3,6 +3,7 @@
 //
 //   cda_square_open / close    da.ExtendShares + NewDataAvailabilityHeader once; the EDS and every node of the 4k
 //                              trees stay in device memory of the handle
+//   cda_square_open_eds        the same for an EDS as it was committed: nothing is extended, the encoding not checked
 //   cda_square_prove           wrapper ErasuredNamespacedMerkleTree.ProveRange (pkg/wrapper/nmt_wrapper.go:127-130) of
 //                              any row or column tree, many ranges per launch
 //   cda_nmt_verify[_device]    nmt Proof.VerifyInclusion as ShareProof.VerifyProof calls it
@@ -66,17 +67,13 @@ void release_squares(cda_ctx* c) {
 
 }  // namespace cda
 
-extern "C" {
+namespace {
 
-int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_t* shares, cda_square** out,
-                    uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
-  CDA_API_TRY
-  set_err(err, CDA_OK, -1, -1, -1, -1);
-  if (out) *out = nullptr;
-  if (!c || !shares || !out || !row_roots || !col_roots || !dah) return CDA_E_ARG;
-  uint32_t k = 0;
-  if (int rc = square_k(count, share_len, &k, err)) return rc;
-  Lock l(c);
+// What cda_square_open and cda_square_open_eds share: the handle's allocation, the commitment of the EDS in it (leaf
+// hash, levels, DAH and data-root tree), the one copy back and the handle.  extended = false: `src` is the k x k ODS
+// and is extended into the EDS area first; true: `src` is the (2k)^2 EDS and is retained as it is.  Lock held.
+int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_square** out, uint8_t* row_roots,
+                uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
   const uint32_t w = 2 * k;
   const int L = ilog2i(w);
   const size_t cells = (size_t)w * w, ods_b = (size_t)k * k * CDA_SHARE, eds_b = cells * CDA_SHARE;
@@ -105,10 +102,13 @@ int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_
   auto level = [&](int h) { return d_levels + square_level_offset(L, h) * CDA_REC_BYTES; };
   hipStream_t s = c->stream;
   int rc;
-  if (!dev_ok(c, hipMemcpyAsync(d_levels, shares, ods_b, hipMemcpyHostToDevice, s), "H2D") ||
-      !dev_ok(c, hipMemsetAsync(d_status, 0xFF, 8, s), "memset"))
-    return CDA_E_DEVICE;
-  if ((rc = enqueue_rs(c, k, 1, d_levels, d_eds, s))) return rc;
+  if (!dev_ok(c, hipMemsetAsync(d_status, 0xFF, 8, s), "memset")) return CDA_E_DEVICE;
+  if (extended) {
+    if ((rc = staged_h2d(c, d_eds, src, eds_b, s))) return rc;
+  } else {
+    if (!dev_ok(c, hipMemcpyAsync(d_levels, src, ods_b, hipMemcpyHostToDevice, s), "H2D")) return CDA_E_DEVICE;
+    if ((rc = enqueue_rs(c, k, 1, d_levels, d_eds, s))) return rc;
+  }
   {
     ProfScope ps(c, "leaf_hash", s);
     if (launch_leaf_hash(d_eds, d_leaf, d_status, (int)k, 1, s)) return CDA_E_DEVICE;
@@ -146,6 +146,35 @@ int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_
   own.sq = nullptr;
   *out = sq;
   return CDA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cda_square_open(cda_ctx* c, uint32_t count, uint32_t share_len, const uint8_t* shares, cda_square** out,
+                    uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
+  CDA_API_TRY
+  set_err(err, CDA_OK, -1, -1, -1, -1);
+  if (out) *out = nullptr;
+  if (!c || !shares || !out || !row_roots || !col_roots || !dah) return CDA_E_ARG;
+  uint32_t k = 0;
+  if (int rc = square_k(count, share_len, &k, err)) return rc;
+  Lock l(c);
+  return open_square(c, k, shares, false, out, row_roots, col_roots, dah, err);
+  CDA_API_CATCH(c)
+}
+
+int cda_square_open_eds(cda_ctx* c, uint32_t k, const uint8_t* eds, cda_square** out, uint8_t* row_roots,
+                        uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
+  CDA_API_TRY
+  set_err(err, CDA_OK, -1, -1, -1, -1);
+  if (out) *out = nullptr;
+  if (!c || !eds || !out || !row_roots || !col_roots || !dah) return CDA_E_ARG;
+  if (!is_pow2(k)) return CDA_E_NOT_POW2;
+  if (k > kMaxDeviceK) return CDA_E_UNSUPPORTED;
+  Lock l(c);
+  return open_square(c, k, eds, true, out, row_roots, col_roots, dah, err);
   CDA_API_CATCH(c)
 }
 

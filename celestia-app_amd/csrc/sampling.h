@@ -1,4 +1,5 @@
-// sampling.h — what sampling.cpp (the C ABI of cda_square_* and cda_nmt_verify*) and sampling_kernels.hip share.
+// sampling.h — what sampling.cpp (the C ABI of cda_square_* and cda_nmt_verify*) and sampling_kernels.hip share, and
+// what befp.cpp (cda_befp_validate*) and befp_kernels.hip share with them and with each other.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -118,5 +119,36 @@ int launch_nmt_verify_namespace(const NsVerifyArgs& a, hipStream_t s);
 
 // ranges = false: no descriptor has more than one leaf (the kernel of the longer proofs is not launched)
 int launch_nmt_verify(const VerifyArgs& a, bool ranges, hipStream_t s);
+
+// cda_befp_validate's arguments, all device memory (include/cda.h), and its workspace (befp.cpp, befp_kernels.hip)
+struct BefpArgs {
+  const cda_befp_desc* descs;
+  const cda_befp_entry* entries;
+  const uint8_t* shares;
+  const uint8_t* nodes;
+  const uint8_t* roots;
+  int32_t* verdicts;
+  uint32_t k, nproofs, nentries, nnodes_total, nroots;
+  // workspace.  Per proof: the verdict of B1 and B2 (befp_rule.h), the decoder's codeword offset and stride, the tree's
+  // axis index, its root record and status word.  Per proof and slot j < 2k: the NMT leg's descriptor, namespace and
+  // verdict of the proof's j-th entry (a slot of its own per proof, so that proofs never share a result), the
+  // decoder's present mask, and the axis buffer [nproofs][2k][512].
+  int32_t* pre;
+  long long* cw_off;
+  long long* cw_stride;
+  unsigned long long* axis_idx;
+  unsigned long long* status;
+  uint8_t* recs;
+  cda_nmt_proof_desc* nmt_descs;
+  uint8_t* nmt_ns;
+  uint8_t* nmt_ok;
+  uint8_t* mask;
+  uint8_t* axes;
+};
+size_t befp_workspace_bytes(uint32_t k, uint32_t nproofs);  // without the axis buffers
+void befp_workspace_bind(BefpArgs& a, void* ws);            // ws: befp_workspace_bytes, 256-byte aligned
+int launch_befp_prep(const BefpArgs& a, hipStream_t s);     // B1, B2; descriptors, namespaces, masks
+int launch_befp_gather(const BefpArgs& a, hipStream_t s);   // entry shares -> axis buffers
+int launch_befp_combine(const BefpArgs& a, hipStream_t s);  // the verdicts
 
 }  // namespace cda

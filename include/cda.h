@@ -311,6 +311,12 @@ typedef struct cda_square cda_square;
  * CDA_E_NS_ORDER mapping, on which no handle is returned); *out receives the handle. */
 int cda_square_open(cda_ctx* ctx, uint32_t count, uint32_t share_len, const uint8_t* shares, cda_square** out,
                     uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah, cda_err_info* err);
+/* Retains a square as it was committed: eds is the whole extended square, (2k)^2 x 512 B row-major in host memory,
+ * k a power of two.  Nothing is extended and the encoding is NOT checked: the handle commits to whatever it was given
+ * (a downloaded or repaired EDS, or a badly encoded one whose cells a bad-encoding fraud proof must carry).  Outputs,
+ * CDA_E_NS_ORDER mapping and every call on the handle as for cda_square_open. */
+int cda_square_open_eds(cda_ctx* ctx, uint32_t k, const uint8_t* eds, cda_square** out, uint8_t* row_roots,
+                        uint8_t* col_roots, uint8_t* dah, cda_err_info* err);
 void cda_square_close(cda_square* sq);
 
 typedef struct {
@@ -479,6 +485,40 @@ int cda_nmt_verify_namespace_device(cda_ctx* ctx, uint32_t nproofs, const void* 
                                     const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
                                     const void* d_leaf_hashes, uint32_t nleaf_hashes, const void* d_leaves,
                                     uint32_t nleaves_total, void* d_ok, void* stream);
+
+/* ---- bad-encoding fraud proofs: batched Validate (specs fraud_proofs.md, rsmt2d ErrByzantineData) ---- */
+/* One proof: axis (axis, index) of a 2k x 2k square, nshares of its cells as entries[entry_off, entry_off + nshares)
+ * in strictly increasing position, each proved against the ORTHOGONAL root; the block's roots are
+ * roots[root_off, root_off + 4k) of 90 B, the 2k row roots then the 2k column roots. */
+typedef struct {
+  uint32_t axis, index, entry_off, nshares, root_off;
+} cda_befp_desc;
+/* Entry e: cell `pos` of the axis, its share shares[512 e, 512 e + 512), the nodes of its proof of leaf
+ * [index, index + 1) in the orthogonal tree nodes[node_off, node_off + nnodes) of 90 B. */
+typedef struct {
+  uint32_t pos, node_off, nnodes;
+} cda_befp_entry;
+#define CDA_BEFP_FRAUD 1       /* the proof holds: the committed axis is not the encoding of its shares */
+#define CDA_BEFP_NO_FRAUD 0    /* the shares rebuild the committed axis root */
+#define CDA_BEFP_MALFORMED -1  /* axis > 1, index >= 2k, nshares > 2k, a position >= 2k or not increasing, or a
+                                  descriptor or entry outside the totals: nothing is read through it */
+#define CDA_BEFP_TOO_FEW -2    /* fewer than k shares */
+#define CDA_BEFP_BAD_SHARE -3  /* a share fails VerifyInclusion against its orthogonal root */
+/* Batched Validate, the first check that applies deciding: MALFORMED, TOO_FEW, BAD_SHARE (the namespace of a share is
+ * its own first 29 bytes if index < k and pos < k, else 0xFF x 29), then the shares are put into 2k slots, the axis
+ * decoded, slots [k, 2k) replaced by the encoding of slots [0, k) and the wrapper tree (squareSize k, axisIndex index)
+ * built: FRAUD if it cannot be built (push order) or its root differs from the committed root of the axis, else
+ * NO_FRAUD.  verdicts[p] (int32); a false proof is a verdict, never an error code.  All proofs of a call share k (a
+ * power of two, else CDA_E_ARG; k <= 512, else CDA_E_UNSUPPORTED); they may belong to different blocks through
+ * root_off.  nentries / nnodes_total / nroots are the totals of entries (and shares) / nodes / roots. */
+int cda_befp_validate(cda_ctx* ctx, uint32_t k, uint32_t nproofs, const cda_befp_desc* descs,
+                      const cda_befp_entry* entries, uint32_t nentries, const uint8_t* shares, const uint8_t* nodes,
+                      uint32_t nnodes_total, const uint8_t* roots, uint32_t nroots, int32_t* verdicts);
+/* The same with every pointer in device memory (d_shares 16-byte, the others 4-byte aligned, else CDA_E_ARG),
+ * asynchronous on `stream`; every check is made in the kernels.  Uses the context's workspace. */
+int cda_befp_validate_device(cda_ctx* ctx, uint32_t k, uint32_t nproofs, const void* d_descs, const void* d_entries,
+                             uint32_t nentries, const void* d_shares, const void* d_nodes, uint32_t nnodes_total,
+                             const void* d_roots, uint32_t nroots, void* d_verdicts, void* stream);
 
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
