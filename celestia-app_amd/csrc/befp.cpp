@@ -12,8 +12,6 @@ using namespace cda;
 
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // k of a call: a power of two the axis-root kernel takes whole (2k leaves in one workgroup's LDS)
 int check_k(uint32_t k, uint32_t nproofs) {
   if (!is_pow2(k)) return CDA_E_ARG;
@@ -24,8 +22,26 @@ int check_k(uint32_t k, uint32_t nproofs) {
 
 int code_of(int lr) { return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE; }
 
-// The seven launches.  a: arguments and workspace bound, a.axes sized [nproofs][2k][512].
-int enqueue_befp(cda_ctx* c, const BefpArgs& a, hipStream_t s) {
+// The arguments of a call as the caller gave them: host pointers in the host form, device pointers in the _device form.
+BefpArgs befp_args(uint32_t k, uint32_t nproofs, const void* descs, const void* entries, uint32_t nentries,
+                   const void* shares, const void* nodes, uint32_t nnodes_total, const void* roots, uint32_t nroots,
+                   void* verdicts) {
+  return BefpArgs{(const cda_befp_desc*)descs, (const cda_befp_entry*)entries, (const uint8_t*)shares,
+                  (const uint8_t*)nodes, (const uint8_t*)roots, (int32_t*)verdicts, k, nproofs, nentries,
+                  nnodes_total, nroots};
+}
+// the sections a call may not leave out
+bool missing(const BefpArgs& a) {
+  return !a.descs || !a.verdicts || (a.nentries && (!a.entries || !a.shares)) || (a.nnodes_total && !a.nodes) ||
+         (a.nroots && !a.roots);
+}
+size_t axes_bytes(const BefpArgs& a) { return (size_t)a.nproofs * 2 * a.k * CDA_SHARE; }
+
+// What both forms end in once every pointer of `a` is device memory: the workspace bound at `ws`, the axis buffers
+// [nproofs][2k][512] in c->scratch (the caller has sized both), the seven launches.
+int enqueue_befp(cda_ctx* c, BefpArgs& a, Arena ws, hipStream_t s) {
+  befp_workspace(a, ws);
+  a.axes = (uint8_t*)c->scratch.p;
   const uint32_t k = a.k, w = 2 * k, slots = a.nproofs * w;
   int lr;
   {
@@ -33,17 +49,8 @@ int enqueue_befp(cda_ctx* c, const BefpArgs& a, hipStream_t s) {
     if (launch_befp_prep(a, s)) return CDA_E_DEVICE;
   }
   {
-    VerifyArgs n{};
-    n.descs = a.nmt_descs;
-    n.namespaces = a.nmt_ns;
-    n.roots = a.roots;
-    n.nodes = a.nodes;
-    n.leaves = a.shares;
-    n.ok = a.nmt_ok;
-    n.nproofs = slots;
-    n.nroots = a.nroots;
-    n.nnodes_total = a.nnodes_total;
-    n.nleaves_total = a.nentries;
+    const VerifyArgs n{a.nmt_descs, a.nmt_ns, a.roots, a.nodes, a.shares, a.nmt_ok, slots, a.nroots, a.nnodes_total,
+                       a.nentries};
     ProfScope ps(c, "befp_nmt_verify", s);
     if (launch_nmt_verify(n, false, s)) return CDA_E_DEVICE;
   }
@@ -96,50 +103,33 @@ int cda_befp_validate(cda_ctx* c, uint32_t k, uint32_t nproofs, const cda_befp_d
   if (!c) return CDA_E_ARG;
   if (int rc = check_k(k, nproofs)) return rc;
   if (nproofs == 0) return CDA_OK;
-  if (!descs || !verdicts || (nentries && (!entries || !shares)) || (nnodes_total && !nodes) || (nroots && !roots))
-    return CDA_E_ARG;
+  const BefpArgs h = befp_args(k, nproofs, descs, entries, nentries, shares, nodes, nnodes_total, roots, nroots,
+                               verdicts);
+  if (missing(h)) return CDA_E_ARG;
   Lock l(c);
   hipStream_t s = c->stream;
-  // descriptors | entries | roots | verdicts | the kernels' workspace, the nodes, the shares, the axis buffers
-  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_befp_desc));
-  const size_t ent_b = align256((size_t)nentries * sizeof(cda_befp_entry));
-  const size_t roots_b = align256((size_t)nroots * CDA_NODE_SIZE), ver_b = align256((size_t)nproofs * 4);
   const size_t nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE, shares_b = (size_t)nentries * CDA_SHARE;
-  int rc;
-  if ((rc = ensure(c, c->plan, desc_b + ent_b + roots_b + ver_b + befp_workspace_bytes(k, nproofs))) ||
-      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, shares_b)) ||
-      (rc = ensure(c, c->scratch, (size_t)nproofs * 2 * k * CDA_SHARE)))
-    return rc;
-  uint8_t* p = (uint8_t*)c->plan.p;
-  auto up = [&](const void* src, size_t n, size_t slot) -> uint8_t* {  // null: the copy failed
-    uint8_t* at = p;
-    p += slot;
-    if (n && !dev_ok(c, hipMemcpyAsync(at, src, n, hipMemcpyHostToDevice, s), "H2D")) return nullptr;
-    return at;
+  BefpArgs a = h;  // the same call on the staged copies; the kernels' workspace follows the verdicts
+  auto lay = [&](Stage& st) {
+    a.descs = st.stage(h.descs, nproofs);
+    a.entries = st.stage(h.entries, nentries);
+    a.roots = st.stage(h.roots, (size_t)nroots * CDA_NODE_SIZE);
+    a.verdicts = st.ar.take<int32_t>(nproofs);
   };
-  BefpArgs a{};
-  a.k = k;
-  a.nproofs = nproofs;
-  a.nentries = nentries;
-  a.nnodes_total = nnodes_total;
-  a.nroots = nroots;
-  if (!(a.descs = (const cda_befp_desc*)up(descs, (size_t)nproofs * sizeof(cda_befp_desc), desc_b)) ||
-      !(a.entries = (const cda_befp_entry*)up(entries, (size_t)nentries * sizeof(cda_befp_entry), ent_b)) ||
-      !(a.roots = up(roots, (size_t)nroots * CDA_NODE_SIZE, roots_b)))
-    return CDA_E_DEVICE;
-  a.verdicts = (int32_t*)p;
-  befp_workspace_bind(a, p + ver_b);
+  int rc;
+  if ((rc = ensure(c, c->plan, staged_bytes(lay) + workspace_bytes(a, befp_workspace))) ||
+      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, shares_b)) ||
+      (rc = ensure(c, c->scratch, axes_bytes(a))))
+    return rc;
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   a.nodes = (const uint8_t*)c->nodes.p;
   a.shares = (const uint8_t*)c->payload.p;
-  a.axes = (uint8_t*)c->scratch.p;
   if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
   if (shares_b && (rc = staged_h2d(c, c->payload.p, shares, shares_b, s))) return rc;
-  if ((rc = enqueue_befp(c, a, s))) return rc;
-  if (!dev_ok(c, hipMemcpyAsync(verdicts, a.verdicts, (size_t)nproofs * 4, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  return CDA_OK;
+  if ((rc = enqueue_befp(c, a, st.ar, s))) return rc;
+  return verdicts_back(c, verdicts, a.verdicts, (size_t)nproofs * 4, s);
   CDA_API_CATCH(c)
 }
 
@@ -150,33 +140,18 @@ int cda_befp_validate_device(cda_ctx* c, uint32_t k, uint32_t nproofs, const voi
   if (!c) return CDA_E_ARG;
   if (int rc = check_k(k, nproofs)) return rc;
   if (nproofs == 0) return CDA_OK;
-  if (!d_descs || !d_verdicts || (nentries && (!d_entries || !d_shares)) || (nnodes_total && !d_nodes) ||
-      (nroots && !d_roots))
-    return CDA_E_ARG;
+  BefpArgs a = befp_args(k, nproofs, d_descs, d_entries, nentries, d_shares, d_nodes, nnodes_total, d_roots, nroots,
+                         d_verdicts);
+  if (missing(a)) return CDA_E_ARG;
   // shares are read 16 bytes at a time, everything else in 4-byte words
   if (((uintptr_t)d_shares & 15) || (((uintptr_t)d_descs | (uintptr_t)d_entries | (uintptr_t)d_nodes |
                                       (uintptr_t)d_roots | (uintptr_t)d_verdicts) & 3))
     return CDA_E_ARG;
-  BefpArgs a{};
-  a.descs = (const cda_befp_desc*)d_descs;
-  a.entries = (const cda_befp_entry*)d_entries;
-  a.shares = (const uint8_t*)d_shares;
-  a.nodes = (const uint8_t*)d_nodes;
-  a.roots = (const uint8_t*)d_roots;
-  a.verdicts = (int32_t*)d_verdicts;
-  a.k = k;
-  a.nproofs = nproofs;
-  a.nentries = nentries;
-  a.nnodes_total = nnodes_total;
-  a.nroots = nroots;
   DevLock dl(c, (hipStream_t)stream);
   int rc;
-  if ((rc = ensure(c, c->plan, befp_workspace_bytes(k, nproofs))) ||
-      (rc = ensure(c, c->scratch, (size_t)nproofs * 2 * k * CDA_SHARE)))
+  if ((rc = ensure(c, c->plan, workspace_bytes(a, befp_workspace))) || (rc = ensure(c, c->scratch, axes_bytes(a))))
     return rc;
-  befp_workspace_bind(a, c->plan.p);
-  a.axes = (uint8_t*)c->scratch.p;
-  return enqueue_befp(c, a, dl.s);
+  return enqueue_befp(c, a, Arena(c->plan.p), dl.s);
   CDA_API_CATCH(c)
 }
 

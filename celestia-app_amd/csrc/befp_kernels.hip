@@ -15,8 +15,6 @@
 namespace cda {
 
 namespace {
-inline size_t ws_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ BefpTotals totals_of(const BefpArgs& a) {
   return BefpTotals{a.k, a.nentries, a.nnodes_total, a.nroots};
 }
@@ -106,32 +104,6 @@ __global__ void __launch_bounds__(256) befp_combine_kernel(BefpArgs a) {
   uint32_t diff = a.status[p] != ~0ull;
   for (uint32_t i = 0; i < CDA_NODE_SIZE; i++) diff |= (uint32_t)(rec[i] ^ want[i]);
   a.verdicts[p] = diff ? CDA_BEFP_FRAUD : CDA_BEFP_NO_FRAUD;
-}
-
-size_t befp_workspace_bytes(uint32_t k, uint32_t nproofs) {
-  const size_t n = nproofs, slots = n * 2 * k;
-  return ws_align(n * 4) + 4 * ws_align(n * 8) + ws_align(n * CDA_REC_BYTES) +
-         ws_align(slots * sizeof(cda_nmt_proof_desc)) + ws_align(slots * CDA_NAMESPACE_SIZE) + 2 * ws_align(slots);
-}
-
-void befp_workspace_bind(BefpArgs& a, void* ws) {
-  const size_t n = a.nproofs, slots = n * 2 * a.k;
-  uint8_t* p = (uint8_t*)ws;
-  auto take = [&](size_t bytes) {
-    uint8_t* at = p;
-    p += ws_align(bytes);
-    return at;
-  };
-  a.pre = (int32_t*)take(n * 4);
-  a.cw_off = (long long*)take(n * 8);
-  a.cw_stride = (long long*)take(n * 8);
-  a.axis_idx = (unsigned long long*)take(n * 8);
-  a.status = (unsigned long long*)take(n * 8);
-  a.recs = take(n * CDA_REC_BYTES);
-  a.nmt_descs = (cda_nmt_proof_desc*)take(slots * sizeof(cda_nmt_proof_desc));
-  a.nmt_ns = take(slots * CDA_NAMESPACE_SIZE);
-  a.nmt_ok = take(slots);
-  a.mask = take(slots);
 }
 
 int launch_befp_prep(const BefpArgs& a, hipStream_t s) {

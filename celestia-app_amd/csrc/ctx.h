@@ -9,6 +9,7 @@
 #include <thread>
 #include <vector>
 
+#include "arena.h"
 #include "cda_internal.h"
 
 namespace cda {
@@ -112,6 +113,36 @@ constexpr int kLdsTreesMax = 512;
 bool dev_ok(cda_ctx* c, hipError_t e, const char* what);
 int ensure(cda_ctx* c, cda_ctx::Buf& b, size_t bytes);
 void flush_profile(cda_ctx* c);
+// Small host arrays of a call into slots of a device buffer (the proof calls' staging in c->plan).  A call states its
+// slots once, as a function of a Stage, and runs it twice: on a measuring arena, which copies nothing, to size the
+// buffer -- ensure may move it, so it comes before the first copy -- and then on the buffer.
+struct Stage {
+  cda_ctx* c;
+  hipStream_t s;
+  Arena ar;
+  bool ok = true;  // false: a copy failed (dev_ok has the error) and none is issued after it
+  template <class T>
+  T* stage(const T* src, size_t count) {
+    T* at = ar.take<T>(count);
+    if (ok && at && count && !dev_ok(c, hipMemcpyAsync(at, src, count * sizeof(T), hipMemcpyHostToDevice, s), "H2D"))
+      ok = false;
+    return at;
+  }
+};
+template <class Lay>
+size_t staged_bytes(Lay& lay) {
+  Stage measure{nullptr, nullptr, Arena()};
+  lay(measure);
+  return measure.ar.used();
+}
+// the end of a host-form verifier: the verdicts back, the call's one wait, the profile
+inline int verdicts_back(cda_ctx* c, void* dst, const void* d_src, size_t n, hipStream_t s) {
+  if (!dev_ok(c, hipMemcpyAsync(dst, d_src, n, hipMemcpyDeviceToHost, s), "D2H") ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  return CDA_OK;
+}
 int ilog2i(uint32_t v);
 bool is_pow2(uint64_t v);
 void set_err(cda_err_info* e, int code, int axis, int index, int leaf, int block);

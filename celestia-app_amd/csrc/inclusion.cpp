@@ -39,8 +39,6 @@ int square_k(uint32_t count, uint32_t share_len, uint32_t* k, cda_err_info* err)
 
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // node (h, p) of a perfect tree of w leaves exported as levels (leaves first, root last), 90 B per node
 const uint8_t* tree_node(const uint8_t* base, uint32_t w, int h, uint32_t p) {
   size_t off = 0;

@@ -16,6 +16,12 @@
 //   cda_nmt_verify_namespace[_device]   nmt Proof.VerifyNamespace (completeness included) of a batch
 // The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.
 //
+// Staging: a call's small arrays go into slots of c->plan that one function of a Stage (ctx.h) states; it runs on a
+// measuring arena to size the buffer, then on the buffer to copy.  Nodes and shares go through staged_h2d into
+// c->nodes and c->payload.  A verifier's host form stages its arrays and then runs what its _device form runs (the
+// *_core functions), with the kernels' workspace after its last slot.  Every ensure of a call comes before its first
+// copy: ensure may move a buffer.
+//
 // Ownership: a square's device memory is one allocation of its own, so no other call on the context can touch it.
 // The context lists its open squares; cda_free releases their device memory and detaches them (ctx = null), after
 // which a handle is good for cda_square_close alone, which then only frees the host struct.  As for every other
@@ -40,8 +46,6 @@ struct cda_square {
 };
 
 namespace {
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 void release_square_memory(cda_square* sq) {
   if (sq->mem) (void)hipFree(sq->mem);
@@ -148,6 +152,61 @@ int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_s
   return CDA_OK;
 }
 
+// ---- the three verifiers.  Per verifier: the arguments of a call as the caller gave them (host pointers in the host
+// form, device pointers in the _device form; the struct's own order), the sections a call may not leave out, and what
+// both forms end in once every pointer is device memory: the workspace bound at `ws`, the launches. ----
+VerifyArgs verify_args(const void* descs, const void* namespaces, const void* roots, const void* nodes,
+                       const void* leaves, void* ok, uint32_t nproofs, uint32_t nroots, uint32_t nnodes_total,
+                       uint32_t nleaves_total) {
+  return VerifyArgs{(const cda_nmt_proof_desc*)descs, (const uint8_t*)namespaces, (const uint8_t*)roots,
+                    (const uint8_t*)nodes, (const uint8_t*)leaves, (uint8_t*)ok, nproofs, nroots, nnodes_total,
+                    nleaves_total};
+}
+bool missing(const VerifyArgs& a) {
+  return !a.descs || !a.namespaces || !a.ok || (a.nroots && !a.roots) || (a.nnodes_total && !a.nodes) ||
+         (a.nleaves_total && !a.leaves);
+}
+int nmt_verify_core(cda_ctx* c, const VerifyArgs& a, bool ranges, hipStream_t s) {
+  ProfScope ps(c, "nmt_verify", s);
+  return launch_nmt_verify(a, ranges, s) ? CDA_E_DEVICE : CDA_OK;
+}
+
+ValidateArgs validate_args(const void* descs, const void* rows, const void* row_roots, const void* leaf_hashes,
+                           const void* nodes, const void* aunts, const void* leaves, const void* data_roots,
+                           void* verdicts, uint32_t nproofs, uint32_t nrows, uint32_t nnodes, uint32_t naunts,
+                           uint32_t nleaves, uint32_t nroots) {
+  return ValidateArgs{(const cda_share_proof_desc*)descs, (const cda_share_row*)rows, (const uint8_t*)row_roots,
+                      (const uint8_t*)leaf_hashes, (const uint8_t*)nodes, (const uint8_t*)aunts,
+                      (const uint8_t*)leaves, (const uint8_t*)data_roots, (int32_t*)verdicts, nproofs, nrows, nnodes,
+                      naunts, nleaves, nroots};
+}
+bool missing(const ValidateArgs& a) {
+  return !a.descs || !a.verdicts || (a.nrows && (!a.rows || !a.row_roots || !a.leaf_hashes)) ||
+         (a.nnodes && !a.nodes) || (a.naunts && !a.aunts) || (a.nleaves && !a.leaves) || (a.nroots && !a.data_roots);
+}
+int share_validate_core(cda_ctx* c, ValidateArgs& a, Arena ws, hipStream_t s) {
+  validate_workspace(a, ws);
+  ProfScope ps(c, "share_proofs_validate", s);
+  return launch_share_proofs_validate(a, s) ? CDA_E_DEVICE : CDA_OK;
+}
+
+NsVerifyArgs ns_verify_args(const void* descs, const void* namespaces, const void* roots, const void* nodes,
+                            const void* leaf_hashes, const void* leaves, void* ok, uint32_t nproofs, uint32_t nroots,
+                            uint32_t nnodes_total, uint32_t nleaf_hashes, uint32_t nleaves_total) {
+  return NsVerifyArgs{(const cda_nmt_ns_proof_desc*)descs, (const uint8_t*)namespaces, (const uint8_t*)roots,
+                      (const uint8_t*)nodes, (const uint8_t*)leaf_hashes, (const uint8_t*)leaves, (uint8_t*)ok,
+                      nproofs, nroots, nnodes_total, nleaf_hashes, nleaves_total};
+}
+bool missing(const NsVerifyArgs& a) {
+  return !a.descs || !a.namespaces || !a.ok || (a.nroots && !a.roots) || (a.nnodes_total && !a.nodes) ||
+         (a.nleaf_hashes && !a.leaf_hashes) || (a.nleaves_total && !a.leaves);
+}
+int ns_verify_core(cda_ctx* c, NsVerifyArgs& a, Arena ws, hipStream_t s) {
+  ns_verify_workspace(a, ws);
+  ProfScope ps(c, "nmt_verify_namespace", s);
+  return launch_nmt_verify_namespace(a, s) ? CDA_E_DEVICE : CDA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -212,18 +271,23 @@ int cda_square_prove(cda_square* sq, uint32_t nq, const cda_range_query* q, uint
   Lock l(c);
   hipStream_t s = c->stream;
   // staging in the context's workspace: queries | counts | share offsets, the nodes, the cells
-  const size_t q_b = align256((size_t)nq * sizeof(cda_range_query)), cnt_b = align256((size_t)nq * 4);
   const size_t nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE, shares_b = shares_or_null ? ncells * CDA_SHARE : 0;
+  const cda_range_query* d_q = nullptr;
+  int32_t* d_counts = nullptr;
+  uint32_t* d_off = nullptr;
+  auto lay = [&](Stage& st) {
+    d_q = st.stage(q, nq);
+    d_counts = st.ar.take<int32_t>(nq);
+    d_off = st.ar.take<uint32_t>(nq);
+  };
   int rc;
-  if ((rc = ensure(c, c->plan, q_b + 2 * cnt_b)) || (rc = ensure(c, c->nodes, nodes_b)) ||
+  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b)) ||
       (shares_b && (rc = ensure(c, c->payload, shares_b))))
     return rc;
-  cda_range_query* d_q = (cda_range_query*)c->plan.p;
-  int32_t* d_counts = (int32_t*)((uint8_t*)c->plan.p + q_b);
-  uint32_t* d_off = (uint32_t*)((uint8_t*)c->plan.p + q_b + cnt_b);
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   uint8_t* d_shares = shares_b ? (uint8_t*)c->payload.p : nullptr;
-  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_range_query), hipMemcpyHostToDevice, s), "H2D"))
-    return CDA_E_DEVICE;
   {
     ProfScope ps(c, "square_prove", s);
     if (launch_square_prove(sq->view, d_q, nq, max_nodes, d_counts, (uint8_t*)c->nodes.p, d_shares ? d_off : nullptr,
@@ -244,8 +308,9 @@ int cda_nmt_verify(cda_ctx* c, uint32_t nproofs, const cda_nmt_proof_desc* descs
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!descs || !namespaces || !ok || (nroots && !roots) || (nnodes_total && !nodes) || (nleaves_total && !leaves))
-    return CDA_E_ARG;
+  const VerifyArgs h = verify_args(descs, namespaces, roots, nodes, leaves, ok, nproofs, nroots, nnodes_total,
+                                   nleaves_total);
+  if (missing(h)) return CDA_E_ARG;
   bool ranges = false;
   for (uint32_t i = 0; i < nproofs; i++) {
     if (descs[i].end > kVerifyMaxEnd) return CDA_E_ARG;
@@ -253,44 +318,27 @@ int cda_nmt_verify(cda_ctx* c, uint32_t nproofs, const cda_nmt_proof_desc* descs
   }
   Lock l(c);
   hipStream_t s = c->stream;
-  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_nmt_proof_desc));
-  const size_t ns_b = align256((size_t)nproofs * CDA_NAMESPACE_SIZE), ok_b = align256(nproofs);
-  const size_t roots_b = (size_t)nroots * CDA_NODE_SIZE, nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE;
-  const size_t leaves_b = (size_t)nleaves_total * CDA_SHARE;
+  const size_t nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE, leaves_b = (size_t)nleaves_total * CDA_SHARE;
+  VerifyArgs a = h;  // the same call on the staged copies
+  auto lay = [&](Stage& st) {
+    a.descs = st.stage(h.descs, nproofs);
+    a.namespaces = st.stage(h.namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE);
+    a.ok = st.ar.take<uint8_t>(nproofs);
+    a.roots = st.stage(h.roots, (size_t)nroots * CDA_NODE_SIZE);
+  };
   int rc;
-  if ((rc = ensure(c, c->plan, desc_b + ns_b + ok_b + align256(roots_b))) || (rc = ensure(c, c->nodes, nodes_b)) ||
+  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b)) ||
       (rc = ensure(c, c->payload, leaves_b)))
     return rc;
-  uint8_t* base = (uint8_t*)c->plan.p;
-  VerifyArgs a{};
-  a.descs = (const cda_nmt_proof_desc*)base;
-  a.namespaces = base + desc_b;
-  a.ok = base + desc_b + ns_b;
-  a.roots = base + desc_b + ns_b + ok_b;
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   a.nodes = (const uint8_t*)c->nodes.p;
   a.leaves = (const uint8_t*)c->payload.p;
-  a.nproofs = nproofs;
-  a.nroots = nroots;
-  a.nnodes_total = nnodes_total;
-  a.nleaves_total = nleaves_total;
-  if (!dev_ok(c, hipMemcpyAsync(base, descs, (size_t)nproofs * sizeof(cda_nmt_proof_desc), hipMemcpyHostToDevice, s),
-              "H2D") ||
-      !dev_ok(c, hipMemcpyAsync(base + desc_b, namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE,
-                                hipMemcpyHostToDevice, s), "H2D") ||
-      (roots_b && !dev_ok(c, hipMemcpyAsync(base + desc_b + ns_b + ok_b, roots, roots_b, hipMemcpyHostToDevice, s),
-                          "H2D")))
-    return CDA_E_DEVICE;
   if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
   if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
-  {
-    ProfScope ps(c, "nmt_verify", s);
-    if (launch_nmt_verify(a, ranges, s)) return CDA_E_DEVICE;
-  }
-  if (!dev_ok(c, hipMemcpyAsync(ok, a.ok, nproofs, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  return CDA_OK;
+  if ((rc = nmt_verify_core(c, a, ranges, s))) return rc;
+  return verdicts_back(c, ok, a.ok, nproofs, s);
   CDA_API_CATCH(c)
 }
 
@@ -300,27 +348,15 @@ int cda_nmt_verify_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, con
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!d_descs || !d_namespaces || !d_ok || (nroots && !d_roots) || (nnodes_total && !d_nodes) ||
-      (nleaves_total && !d_leaves))
-    return CDA_E_ARG;
+  const VerifyArgs a = verify_args(d_descs, d_namespaces, d_roots, d_nodes, d_leaves, d_ok, nproofs, nroots,
+                                   nnodes_total, nleaves_total);
+  if (missing(a)) return CDA_E_ARG;
   // the kernels read shares 16 bytes and nodes, roots and descriptors 4 bytes at a time
   if (((uintptr_t)d_leaves & 15) || (((uintptr_t)d_nodes | (uintptr_t)d_roots | (uintptr_t)d_descs) & 3))
     return CDA_E_ARG;
-  VerifyArgs a{};
-  a.descs = (const cda_nmt_proof_desc*)d_descs;
-  a.namespaces = (const uint8_t*)d_namespaces;
-  a.roots = (const uint8_t*)d_roots;
-  a.nodes = (const uint8_t*)d_nodes;
-  a.leaves = (const uint8_t*)d_leaves;
-  a.ok = (uint8_t*)d_ok;
-  a.nproofs = nproofs;
-  a.nroots = nroots;
-  a.nnodes_total = nnodes_total;
-  a.nleaves_total = nleaves_total;
   DevLock dl(c, (hipStream_t)stream);
-  ProfScope ps(c, "nmt_verify", dl.s);
   // the descriptors are device memory: whether any proof has more than one leaf is not known here
-  return launch_nmt_verify(a, true, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  return nmt_verify_core(c, a, true, dl.s);
   CDA_API_CATCH(c)
 }
 
@@ -354,27 +390,28 @@ int cda_square_share_proofs(cda_square* sq, uint32_t nq, const cda_share_range* 
   hipStream_t s = c->stream;
   // staging in the context's workspace: queries | offsets | row records | row roots | leaf hashes | aunts, the nodes,
   // the shares
-  const size_t q_b = align256((size_t)nq * sizeof(cda_share_range)), off_b = align256(off.size() * 4);
-  const size_t rows_b = align256(nrows * sizeof(cda_share_row)), roots_b = align256(nrows * CDA_NODE_SIZE);
-  const size_t lh_b = align256(nrows * 32), aunts_b = nrows * naunts * 32;
+  const size_t aunts_b = nrows * naunts * 32;
   const size_t nodes_b = nrows * max_nodes * CDA_NODE_SIZE, shares_b = shares_or_null ? nshares * CDA_SHARE : 0;
-  int rc;
-  if ((rc = ensure(c, c->plan, q_b + off_b + rows_b + roots_b + lh_b + aunts_b)) ||
-      (rc = ensure(c, c->nodes, nodes_b)) || (shares_b && (rc = ensure(c, c->payload, shares_b))))
-    return rc;
-  uint8_t* base = (uint8_t*)c->plan.p;
-  cda_share_range* d_q = (cda_share_range*)base;
-  uint32_t* d_off = (uint32_t*)(base + q_b);
+  const cda_share_range* d_q = nullptr;
+  const uint32_t* d_off = nullptr;
   ShareProofsOut o{};
-  o.rows = (cda_share_row*)(base + q_b + off_b);
-  o.row_roots = base + q_b + off_b + rows_b;
-  o.leaf_hashes = o.row_roots + roots_b;
-  o.aunts = o.leaf_hashes + lh_b;
+  auto lay = [&](Stage& st) {
+    d_q = st.stage(q, nq);
+    d_off = st.stage(off.data(), off.size());
+    o.rows = st.ar.take<cda_share_row>(nrows);
+    o.row_roots = st.ar.take<uint8_t>(nrows * CDA_NODE_SIZE);
+    o.leaf_hashes = st.ar.take<uint8_t>(nrows * 32);
+    o.aunts = st.ar.take<uint8_t>(aunts_b);
+  };
+  int rc;
+  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b)) ||
+      (shares_b && (rc = ensure(c, c->payload, shares_b))))
+    return rc;
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   o.nodes = (uint8_t*)c->nodes.p;
   o.shares = shares_b ? (uint8_t*)c->payload.p : nullptr;
-  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_share_range), hipMemcpyHostToDevice, s), "H2D") ||
-      !dev_ok(c, hipMemcpyAsync(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, s), "H2D"))
-    return CDA_E_DEVICE;
   {
     ProfScope ps(c, "square_share_proofs", s);
     if (launch_square_share_proofs(sq->view, d_q, nq, d_off, d_off + nq + 1, (uint32_t)nrows, max_nodes, o, s))
@@ -401,57 +438,35 @@ int cda_share_proofs_validate(cda_ctx* c, uint32_t nproofs, const cda_share_proo
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!descs || !verdicts || (nrows && (!rows || !row_roots || !leaf_hashes)) || (nnodes && !nodes) ||
-      (naunts && !aunts) || (nleaves && !leaves) || (nroots && !data_roots))
-    return CDA_E_ARG;
+  const ValidateArgs h = validate_args(descs, rows, row_roots, leaf_hashes, nodes, aunts, leaves, data_roots, verdicts,
+                                       nproofs, nrows, nnodes, naunts, nleaves, nroots);
+  if (missing(h)) return CDA_E_ARG;
   Lock l(c);
   hipStream_t s = c->stream;
-  // descriptors | row records | row roots | leaf hashes | aunts | data roots | verdicts | the kernels' workspace
-  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_share_proof_desc));
-  const size_t rows_b = align256((size_t)nrows * sizeof(cda_share_row));
-  const size_t rr_b = align256((size_t)nrows * CDA_NODE_SIZE), lh_b = align256((size_t)nrows * 32);
-  const size_t aunts_b = align256((size_t)naunts * 32), dr_b = align256((size_t)nroots * 32);
-  const size_t ver_b = align256((size_t)nproofs * 4), ws_b = validate_workspace_bytes(nproofs, nrows);
   const size_t nodes_b = (size_t)nnodes * CDA_NODE_SIZE, leaves_b = (size_t)nleaves * CDA_SHARE;
+  ValidateArgs a = h;  // the same call on the staged copies; the kernels' workspace follows the verdicts
+  auto lay = [&](Stage& st) {
+    a.descs = st.stage(h.descs, nproofs);
+    a.rows = st.stage(h.rows, nrows);
+    a.row_roots = st.stage(h.row_roots, (size_t)nrows * CDA_NODE_SIZE);
+    a.leaf_hashes = st.stage(h.leaf_hashes, (size_t)nrows * 32);
+    a.aunts = st.stage(h.aunts, (size_t)naunts * 32);
+    a.data_roots = st.stage(h.data_roots, (size_t)nroots * 32);
+    a.verdicts = st.ar.take<int32_t>(nproofs);
+  };
   int rc;
-  if ((rc = ensure(c, c->plan, desc_b + rows_b + rr_b + lh_b + aunts_b + dr_b + ver_b + ws_b)) ||
+  if ((rc = ensure(c, c->plan, staged_bytes(lay) + workspace_bytes(a, validate_workspace))) ||
       (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
     return rc;
-  uint8_t* p = (uint8_t*)c->plan.p;
-  auto up = [&](const void* src, size_t n, size_t slot) -> uint8_t* {  // null: the copy failed
-    uint8_t* at = p;
-    p += slot;
-    if (n && !dev_ok(c, hipMemcpyAsync(at, src, n, hipMemcpyHostToDevice, s), "H2D")) return nullptr;
-    return at;
-  };
-  ValidateArgs a{};
-  a.nproofs = nproofs;
-  a.nrows = nrows;
-  a.nnodes = nnodes;
-  a.naunts = naunts;
-  a.nleaves = nleaves;
-  a.nroots = nroots;
-  if (!(a.descs = (const cda_share_proof_desc*)up(descs, (size_t)nproofs * sizeof(cda_share_proof_desc), desc_b)) ||
-      !(a.rows = (const cda_share_row*)up(rows, (size_t)nrows * sizeof(cda_share_row), rows_b)) ||
-      !(a.row_roots = up(row_roots, (size_t)nrows * CDA_NODE_SIZE, rr_b)) ||
-      !(a.leaf_hashes = up(leaf_hashes, (size_t)nrows * 32, lh_b)) ||
-      !(a.aunts = up(aunts, (size_t)naunts * 32, aunts_b)) || !(a.data_roots = up(data_roots, (size_t)nroots * 32, dr_b)))
-    return CDA_E_DEVICE;
-  a.verdicts = (int32_t*)p;
-  validate_workspace_bind(a, p + ver_b);
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   a.nodes = (const uint8_t*)c->nodes.p;
   a.leaves = (const uint8_t*)c->payload.p;
   if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
   if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
-  {
-    ProfScope ps(c, "share_proofs_validate", s);
-    if (launch_share_proofs_validate(a, s)) return CDA_E_DEVICE;
-  }
-  if (!dev_ok(c, hipMemcpyAsync(verdicts, a.verdicts, (size_t)nproofs * 4, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  return CDA_OK;
+  if ((rc = share_validate_core(c, a, st.ar, s))) return rc;
+  return verdicts_back(c, verdicts, a.verdicts, (size_t)nproofs * 4, s);
   CDA_API_CATCH(c)
 }
 
@@ -463,35 +478,17 @@ int cda_share_proofs_validate_device(cda_ctx* c, uint32_t nproofs, const void* d
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!d_descs || !d_verdicts || (nrows && (!d_rows || !d_row_roots || !d_leaf_hashes)) || (nnodes && !d_nodes) ||
-      (naunts && !d_aunts) || (nleaves && !d_leaves) || (nroots && !d_data_roots))
-    return CDA_E_ARG;
+  ValidateArgs a = validate_args(d_descs, d_rows, d_row_roots, d_leaf_hashes, d_nodes, d_aunts, d_leaves, d_data_roots,
+                                 d_verdicts, nproofs, nrows, nnodes, naunts, nleaves, nroots);
+  if (missing(a)) return CDA_E_ARG;
   // shares are read 16 bytes at a time, row records hold 64-bit fields, everything else is read in 4-byte words
   if (((uintptr_t)d_leaves & 15) || ((uintptr_t)d_rows & 7) ||
       (((uintptr_t)d_descs | (uintptr_t)d_row_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_nodes |
         (uintptr_t)d_aunts | (uintptr_t)d_data_roots | (uintptr_t)d_verdicts) & 3))
     return CDA_E_ARG;
-  ValidateArgs a{};
-  a.descs = (const cda_share_proof_desc*)d_descs;
-  a.rows = (const cda_share_row*)d_rows;
-  a.row_roots = (const uint8_t*)d_row_roots;
-  a.leaf_hashes = (const uint8_t*)d_leaf_hashes;
-  a.nodes = (const uint8_t*)d_nodes;
-  a.aunts = (const uint8_t*)d_aunts;
-  a.leaves = (const uint8_t*)d_leaves;
-  a.data_roots = (const uint8_t*)d_data_roots;
-  a.verdicts = (int32_t*)d_verdicts;
-  a.nproofs = nproofs;
-  a.nrows = nrows;
-  a.nnodes = nnodes;
-  a.naunts = naunts;
-  a.nleaves = nleaves;
-  a.nroots = nroots;
   DevLock dl(c, (hipStream_t)stream);
-  if (int rc = ensure(c, c->plan, validate_workspace_bytes(nproofs, nrows))) return rc;
-  validate_workspace_bind(a, c->plan.p);
-  ProfScope ps(c, "share_proofs_validate", dl.s);
-  return launch_share_proofs_validate(a, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  if (int rc = ensure(c, c->plan, workspace_bytes(a, validate_workspace))) return rc;
+  return share_validate_core(c, a, Arena(c->plan.p), dl.s);
   CDA_API_CATCH(c)
 }
 
@@ -513,18 +510,22 @@ int cda_square_prove_namespace(cda_square* sq, uint32_t nq, const cda_namespace_
   Lock l(c);
   hipStream_t s = c->stream;
   // staging in the context's workspace: queries | results | leaf hashes | the share total, the nodes, the shares
-  const size_t q_b = align256((size_t)nq * sizeof(cda_namespace_query));
-  const size_t res_b = align256((size_t)nq * sizeof(cda_namespace_result));
-  const size_t lh_b = align256((size_t)nq * CDA_NODE_SIZE), nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE;
+  const size_t nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE;
+  const cda_namespace_query* d_q = nullptr;
+  cda_namespace_result* d_res = nullptr;
+  uint8_t* d_lh = nullptr;
+  unsigned long long* d_total = nullptr;
+  auto lay = [&](Stage& st) {
+    d_q = st.stage(q, nq);
+    d_res = st.ar.take<cda_namespace_result>(nq);
+    d_lh = st.ar.take<uint8_t>((size_t)nq * CDA_NODE_SIZE);
+    d_total = st.ar.take<unsigned long long>(1);
+  };
   int rc;
-  if ((rc = ensure(c, c->plan, q_b + res_b + lh_b + 256)) || (rc = ensure(c, c->nodes, nodes_b))) return rc;
-  uint8_t* base = (uint8_t*)c->plan.p;
-  cda_namespace_query* d_q = (cda_namespace_query*)base;
-  cda_namespace_result* d_res = (cda_namespace_result*)(base + q_b);
-  uint8_t* d_lh = base + q_b + res_b;
-  unsigned long long* d_total = (unsigned long long*)(d_lh + lh_b);
-  if (!dev_ok(c, hipMemcpyAsync(d_q, q, (size_t)nq * sizeof(cda_namespace_query), hipMemcpyHostToDevice, s), "H2D"))
-    return CDA_E_DEVICE;
+  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b))) return rc;
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   {
     ProfScope ps(c, "square_prove_namespace", s);
     if (launch_square_prove_namespace(sq->view, d_q, nq, max_nodes, d_res, (uint8_t*)c->nodes.p, d_lh, d_total, s))
@@ -564,58 +565,35 @@ int cda_nmt_verify_namespace(cda_ctx* c, uint32_t nproofs, const cda_nmt_ns_proo
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!descs || !namespaces || !ok || (nroots && !roots) || (nnodes_total && !nodes) ||
-      (nleaf_hashes && !leaf_hashes) || (nleaves_total && !leaves))
-    return CDA_E_ARG;
+  const NsVerifyArgs h = ns_verify_args(descs, namespaces, roots, nodes, leaf_hashes, leaves, ok, nproofs, nroots,
+                                        nnodes_total, nleaf_hashes, nleaves_total);
+  if (missing(h)) return CDA_E_ARG;
   for (uint32_t i = 0; i < nproofs; i++)
     if (descs[i].end > kVerifyMaxEnd) return CDA_E_ARG;
   Lock l(c);
   hipStream_t s = c->stream;
-  // descriptors | namespaces | verdicts | roots | leaf hashes | the kernels' workspace, the nodes, the leaves
-  const size_t desc_b = align256((size_t)nproofs * sizeof(cda_nmt_ns_proof_desc));
-  const size_t ns_b = align256((size_t)nproofs * CDA_NAMESPACE_SIZE), ok_b = align256(nproofs);
-  const size_t roots_b = (size_t)nroots * CDA_NODE_SIZE, lh_b = (size_t)nleaf_hashes * CDA_NODE_SIZE;
   const size_t nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE, leaves_b = (size_t)nleaves_total * CDA_SHARE;
+  NsVerifyArgs a = h;  // the same call on the staged copies; the kernels' workspace follows the leaf hashes
+  auto lay = [&](Stage& st) {
+    a.descs = st.stage(h.descs, nproofs);
+    a.namespaces = st.stage(h.namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE);
+    a.ok = st.ar.take<uint8_t>(nproofs);
+    a.roots = st.stage(h.roots, (size_t)nroots * CDA_NODE_SIZE);
+    a.leaf_hashes = st.stage(h.leaf_hashes, (size_t)nleaf_hashes * CDA_NODE_SIZE);
+  };
   int rc;
-  if ((rc = ensure(c, c->plan,
-                   desc_b + ns_b + ok_b + align256(roots_b) + align256(lh_b) + ns_verify_workspace_bytes(nproofs))) ||
+  if ((rc = ensure(c, c->plan, staged_bytes(lay) + workspace_bytes(a, ns_verify_workspace))) ||
       (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
     return rc;
-  uint8_t* base = (uint8_t*)c->plan.p;
-  uint8_t* d_roots = base + desc_b + ns_b + ok_b;
-  uint8_t* d_lh = d_roots + align256(roots_b);
-  NsVerifyArgs a{};
-  a.descs = (const cda_nmt_ns_proof_desc*)base;
-  a.namespaces = base + desc_b;
-  a.ok = base + desc_b + ns_b;
-  a.roots = d_roots;
-  a.leaf_hashes = d_lh;
+  Stage st{c, s, Arena(c->plan.p)};
+  lay(st);
+  if (!st.ok) return CDA_E_DEVICE;
   a.nodes = (const uint8_t*)c->nodes.p;
   a.leaves = (const uint8_t*)c->payload.p;
-  a.nproofs = nproofs;
-  a.nroots = nroots;
-  a.nnodes_total = nnodes_total;
-  a.nleaf_hashes = nleaf_hashes;
-  a.nleaves_total = nleaves_total;
-  ns_verify_workspace_bind(a, d_lh + align256(lh_b));
-  if (!dev_ok(c, hipMemcpyAsync(base, descs, (size_t)nproofs * sizeof(cda_nmt_ns_proof_desc), hipMemcpyHostToDevice, s),
-              "H2D") ||
-      !dev_ok(c, hipMemcpyAsync(base + desc_b, namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE,
-                                hipMemcpyHostToDevice, s), "H2D") ||
-      (roots_b && !dev_ok(c, hipMemcpyAsync(d_roots, roots, roots_b, hipMemcpyHostToDevice, s), "H2D")) ||
-      (lh_b && !dev_ok(c, hipMemcpyAsync(d_lh, leaf_hashes, lh_b, hipMemcpyHostToDevice, s), "H2D")))
-    return CDA_E_DEVICE;
   if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
   if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
-  {
-    ProfScope ps(c, "nmt_verify_namespace", s);
-    if (launch_nmt_verify_namespace(a, s)) return CDA_E_DEVICE;
-  }
-  if (!dev_ok(c, hipMemcpyAsync(ok, a.ok, nproofs, hipMemcpyDeviceToHost, s), "D2H") ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  return CDA_OK;
+  if ((rc = ns_verify_core(c, a, st.ar, s))) return rc;
+  return verdicts_back(c, ok, a.ok, nproofs, s);
   CDA_API_CATCH(c)
 }
 
@@ -626,31 +604,16 @@ int cda_nmt_verify_namespace_device(cda_ctx* c, uint32_t nproofs, const void* d_
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
   if (nproofs == 0) return CDA_OK;
-  if (!d_descs || !d_namespaces || !d_ok || (nroots && !d_roots) || (nnodes_total && !d_nodes) ||
-      (nleaf_hashes && !d_leaf_hashes) || (nleaves_total && !d_leaves))
-    return CDA_E_ARG;
+  NsVerifyArgs a = ns_verify_args(d_descs, d_namespaces, d_roots, d_nodes, d_leaf_hashes, d_leaves, d_ok, nproofs,
+                                  nroots, nnodes_total, nleaf_hashes, nleaves_total);
+  if (missing(a)) return CDA_E_ARG;
   // the kernels read shares 16 bytes and nodes, roots, leaf hashes and descriptors 4 bytes at a time
   if (((uintptr_t)d_leaves & 15) ||
       (((uintptr_t)d_nodes | (uintptr_t)d_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_descs) & 3))
     return CDA_E_ARG;
-  NsVerifyArgs a{};
-  a.descs = (const cda_nmt_ns_proof_desc*)d_descs;
-  a.namespaces = (const uint8_t*)d_namespaces;
-  a.roots = (const uint8_t*)d_roots;
-  a.nodes = (const uint8_t*)d_nodes;
-  a.leaf_hashes = (const uint8_t*)d_leaf_hashes;
-  a.leaves = (const uint8_t*)d_leaves;
-  a.ok = (uint8_t*)d_ok;
-  a.nproofs = nproofs;
-  a.nroots = nroots;
-  a.nnodes_total = nnodes_total;
-  a.nleaf_hashes = nleaf_hashes;
-  a.nleaves_total = nleaves_total;
   DevLock dl(c, (hipStream_t)stream);
-  if (int rc = ensure(c, c->plan, ns_verify_workspace_bytes(nproofs))) return rc;
-  ns_verify_workspace_bind(a, c->plan.p);
-  ProfScope ps(c, "nmt_verify_namespace", dl.s);
-  return launch_nmt_verify_namespace(a, dl.s) ? CDA_E_DEVICE : CDA_OK;
+  if (int rc = ensure(c, c->plan, workspace_bytes(a, ns_verify_workspace))) return rc;
+  return ns_verify_core(c, a, Arena(c->plan.p), dl.s);
   CDA_API_CATCH(c)
 }
 

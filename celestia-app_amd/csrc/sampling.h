@@ -1,11 +1,14 @@
 // sampling.h — what sampling.cpp (the C ABI of cda_square_* and cda_nmt_verify*) and sampling_kernels.hip share, and
-// what befp.cpp (cda_befp_validate*) and befp_kernels.hip share with them and with each other.
+// what befp.cpp (cda_befp_validate*) and befp_kernels.hip share with them and with each other: the argument structs
+// the kernels take, the layouts of the verifiers' workspaces and the launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/cda.h"
+#include "arena.h"
+#include "cda_internal.h"
 
 namespace cda {
 
@@ -57,7 +60,15 @@ int launch_square_share_proofs(const SquareView& v, const cda_share_range* d_q, 
                                const uint32_t* d_share_off, uint32_t nrows, uint32_t max_nodes,
                                const ShareProofsOut& out, hipStream_t s);
 
-// cda_share_proofs_validate's arguments, all device memory (include/cda.h), and its workspace
+// cda_share_proofs_validate's arguments, all device memory (include/cda.h), and its workspace.  Each workspace of this
+// header has one statement of its layout, a walk over an Arena (arena.h): on a measuring arena it sizes the workspace,
+// on the buffer it points the struct's workspace fields into it.
+template <class Args>
+size_t workspace_bytes(Args a, void (*layout)(Args&, Arena&)) {  // a: the counts the layout reads
+  Arena measure;
+  layout(a, measure);
+  return measure.used();
+}
 struct ValidateArgs {
   const cda_share_proof_desc* descs;
   const cda_share_row* rows;
@@ -79,9 +90,18 @@ struct ValidateArgs {
   uint8_t* nmt_ok;
   uint8_t* row_ok;
 };
-size_t validate_workspace_bytes(uint32_t nproofs, uint32_t nrows);
-// points a's workspace fields into `ws` (validate_workspace_bytes, 256-byte aligned)
-void validate_workspace_bind(ValidateArgs& a, void* ws);
+// The layout, from a.nproofs and a.nrows.  launch_share_proofs_validate clears the whole of it in one memset that
+// starts at its first slot, `pre`: a slot added here is cleared with the others, and none may come before `pre`.
+inline void validate_workspace(ValidateArgs& a, Arena& ws) {
+  const size_t n = a.nrows;
+  a.pre = ws.take<int32_t>(a.nproofs);
+  a.owner = ws.take<uint32_t>(n);
+  a.claims = ws.take<uint32_t>(n);
+  a.nmt_descs = ws.take<cda_nmt_proof_desc>(n);
+  a.nmt_ns = ws.take<uint8_t>(n * CDA_NAMESPACE_SIZE);
+  a.nmt_ok = ws.take<uint8_t>(n);
+  a.row_ok = ws.take<uint8_t>(n);
+}
 // the three legs: counting checks and NMT descriptors, launch_nmt_verify over the row records, one Proof.Verify per
 // lane; then the per-proof verdict
 int launch_share_proofs_validate(const ValidateArgs& a, hipStream_t s);
@@ -112,8 +132,12 @@ struct NsVerifyArgs {
   uint8_t* nmt_ok;
   uint8_t* abs_ok;
 };
-size_t ns_verify_workspace_bytes(uint32_t nproofs);
-void ns_verify_workspace_bind(NsVerifyArgs& a, void* ws);  // ws: ns_verify_workspace_bytes, 256-byte aligned
+inline void ns_verify_workspace(NsVerifyArgs& a, Arena& ws) {  // the layout, from a.nproofs
+  a.nmt_descs = ws.take<cda_nmt_proof_desc>(a.nproofs);
+  a.pre = ws.take<uint8_t>(a.nproofs);
+  a.nmt_ok = ws.take<uint8_t>(a.nproofs);
+  a.abs_ok = ws.take<uint8_t>(a.nproofs);
+}
 // prep (V1-V5), launch_nmt_verify over the inclusion proofs, the absence chains, combine
 int launch_nmt_verify_namespace(const NsVerifyArgs& a, hipStream_t s);
 
@@ -145,8 +169,19 @@ struct BefpArgs {
   uint8_t* mask;
   uint8_t* axes;
 };
-size_t befp_workspace_bytes(uint32_t k, uint32_t nproofs);  // without the axis buffers
-void befp_workspace_bind(BefpArgs& a, void* ws);            // ws: befp_workspace_bytes, 256-byte aligned
+inline void befp_workspace(BefpArgs& a, Arena& ws) {  // the layout, from a.k and a.nproofs; without the axis buffers
+  const size_t n = a.nproofs, slots = n * 2 * a.k;
+  a.pre = ws.take<int32_t>(n);
+  a.cw_off = ws.take<long long>(n);
+  a.cw_stride = ws.take<long long>(n);
+  a.axis_idx = ws.take<unsigned long long>(n);
+  a.status = ws.take<unsigned long long>(n);
+  a.recs = ws.take<uint8_t>(n * CDA_REC_BYTES);
+  a.nmt_descs = ws.take<cda_nmt_proof_desc>(slots);
+  a.nmt_ns = ws.take<uint8_t>(slots * CDA_NAMESPACE_SIZE);
+  a.nmt_ok = ws.take<uint8_t>(slots);
+  a.mask = ws.take<uint8_t>(slots);
+}
 int launch_befp_prep(const BefpArgs& a, hipStream_t s);     // B1, B2; descriptors, namespaces, masks
 int launch_befp_gather(const BefpArgs& a, hipStream_t s);   // entry shares -> axis buffers
 int launch_befp_combine(const BefpArgs& a, hipStream_t s);  // the verdicts

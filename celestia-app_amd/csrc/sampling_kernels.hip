@@ -649,38 +649,10 @@ __global__ void __launch_bounds__(256) share_validate_combine_kernel(ValidateArg
   a.verdicts[p] = v;
 }
 
-namespace {
-inline size_t ws_align(size_t v) { return (v + 255) & ~(size_t)255; }
-}  // namespace
-
-size_t validate_workspace_bytes(uint32_t nproofs, uint32_t nrows) {
-  const size_t n = nrows;
-  return ws_align((size_t)nproofs * 4) + 2 * ws_align(n * 4) + ws_align(n * sizeof(cda_nmt_proof_desc)) +
-         ws_align(n * CDA_NAMESPACE_SIZE) + 2 * ws_align(n);
-}
-
-void validate_workspace_bind(ValidateArgs& a, void* ws) {
-  uint8_t* p = (uint8_t*)ws;
-  const size_t n = a.nrows;
-  a.pre = (int32_t*)p;
-  p += ws_align((size_t)a.nproofs * 4);
-  a.owner = (uint32_t*)p;
-  p += ws_align(n * 4);
-  a.claims = (uint32_t*)p;
-  p += ws_align(n * 4);
-  a.nmt_descs = (cda_nmt_proof_desc*)p;
-  p += ws_align(n * sizeof(cda_nmt_proof_desc));
-  a.nmt_ns = p;
-  p += ws_align(n * CDA_NAMESPACE_SIZE);
-  a.nmt_ok = p;
-  p += ws_align(n);
-  a.row_ok = p;
-}
-
 int launch_share_proofs_validate(const ValidateArgs& a, hipStream_t s) {
   if (a.nproofs == 0) return 0;
   // everything zero (no claims, empty NMT descriptors, verdicts "fails") but the owners: none
-  if (hipMemsetAsync(a.pre, 0, validate_workspace_bytes(a.nproofs, a.nrows), s) != hipSuccess) return -1;
+  if (hipMemsetAsync(a.pre, 0, workspace_bytes(a, validate_workspace), s) != hipSuccess) return -1;
   if (a.nrows && hipMemsetAsync(a.owner, 0xFF, (size_t)a.nrows * 4, s) != hipSuccess) return -1;
   const dim3 pgrid((a.nproofs + 255) / 256), block(256);
   hipLaunchKernelGGL(share_validate_prep_kernel, pgrid, block, 0, s, a);
@@ -918,21 +890,6 @@ __global__ void __launch_bounds__(256) ns_verify_combine_kernel(NsVerifyArgs a) 
   else if (pre == kNsInclusion) ok = a.nmt_ok[p] ? 1 : 0;
   else if (pre == kNsAbsence) ok = a.abs_ok[p] ? 1 : 0;
   a.ok[p] = ok;
-}
-
-size_t ns_verify_workspace_bytes(uint32_t nproofs) {
-  return ws_align((size_t)nproofs * sizeof(cda_nmt_proof_desc)) + 3 * ws_align(nproofs);
-}
-
-void ns_verify_workspace_bind(NsVerifyArgs& a, void* ws) {
-  uint8_t* p = (uint8_t*)ws;
-  a.nmt_descs = (cda_nmt_proof_desc*)p;
-  p += ws_align((size_t)a.nproofs * sizeof(cda_nmt_proof_desc));
-  a.pre = p;
-  p += ws_align(a.nproofs);
-  a.nmt_ok = p;
-  p += ws_align(a.nproofs);
-  a.abs_ok = p;
 }
 
 int launch_nmt_verify_namespace(const NsVerifyArgs& a, hipStream_t s) {
