@@ -76,9 +76,10 @@ int launch_leaf_hash(const uint8_t* d_eds, void* d_leaf_nodes, unsigned long lon
                      hipStream_t s);
 int launch_nmt_level(const void* d_in, void* d_out, bool from_leaves, int k, int nblocks, int level, hipStream_t s);
 // Leaf records -> all 4k roots of nblocks blocks, several levels per launch; d_levels: nblocks x 2w x w
-// records of scratch for the inner levels.  prof_ctx: the cda_ctx for ProfScope (or null).
+// records of scratch for the inner levels.  prof_ctx: the cda_ctx for ProfScope (or null).  l1_quads: level 1 from
+// nmt_level1_quads_kernel (trees of at least 4 leaves); false is the A/B form, levels 1-2 in one nmt_levels_kernel launch.
 int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k, int nblocks, hipStream_t s,
-                     void* prof_ctx);
+                     void* prof_ctx, bool l1_quads = true);
 int launch_dah(const void* d_roots, void* d_dah, int n_roots_total, int nblocks, hipStream_t s);
 // launch_dah of one block that also writes the whole RFC-6962 tree (2n - 1 digests of 32 B, leaf hashes first, the
 // root last) to d_nodes_out

@@ -33,6 +33,8 @@ struct cda_ctx {
   bool repair_fused_verify = true;
   // CDA_REPAIR_EARLY=0: repair copies the square back only at the end (no early row return)
   bool repair_early = true;
+  // CDA_L1_QUADS=0: tree levels 1-2 in one nmt_levels_kernel launch instead of the quad kernel + a level-2 launch
+  bool l1_quads = true;
   // HIP maps streams round-robin onto GPU_MAX_HW_QUEUES (4) hardware queues, so the streams that must run
   // concurrently are created first, together: stream, h2d_stream, d2h_stream, aux_stream.
   hipStream_t aux_stream = nullptr;

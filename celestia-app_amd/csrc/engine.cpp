@@ -7,7 +7,8 @@
 //   2. rs_encode8  columns  : EDS column c of [Q0|Q1] -> [Q2|Q3] column c  (2k codewords / block)
 //      (Q3 = Enc(Q2 rows) in rsmt2d; by linearity Enc_col(Q1) is the same bytes)
 //   3. leaf_hash            : every EDS cell once -> 96-B leaf records + namespace-order status
-//   4. nmt_levels           : row and column trees of every block, 2 (or 3) levels per launch
+//   4. nmt_levels           : row and column trees of every block: level 1 by 2x2 cell quads, level 2, then 2 (or 3)
+//                             levels per launch
 //   5. dah                  : RFC-6962 over row roots ‖ col roots
 // rsmt2d Repair lives in repair.cpp, the host-buffer batch pipeline in host_pipeline.cpp.
 // Nothing here computes on the CPU: the host only validates arguments, moves
@@ -239,7 +240,7 @@ int enqueue_trees(cda_ctx* c, uint32_t k, uint32_t nblocks, void* d_roots, void*
   // inner levels in c->scratch: 2 records per leaf record of the chunk (2w x (w - 2) per block)
   const int lr0 = launch_nmt_trees((uint8_t*)c->leaf.p + rec_off * CDA_REC_BYTES,
                                    (uint8_t*)c->scratch.p + 2 * rec_off * CDA_REC_BYTES, d_roots, (int)k, (int)nblocks, s,
-                                   c);
+                                   c, c->l1_quads);
   if (lr0) return lr0 == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;
   if (w < 1024) {  // k <= 256: one workgroup per block (the wide form's agent-scope release of the digests cost
                    // more than its 4 -> 2 digest compressions saved: 0.077 -> 0.112 ms per B = 128 step at k = 128)
@@ -331,6 +332,7 @@ int cda_init(int device, cda_ctx** out) {
   if (const char* e = CDA_AB_ENV("CDA_REPAIR_OVERLAP")) c->repair_overlap = atoi(e) != 0;
   if (const char* e = CDA_AB_ENV("CDA_REPAIR_FUSED")) c->repair_fused_verify = atoi(e) != 0;
   if (const char* e = CDA_AB_ENV("CDA_REPAIR_EARLY")) c->repair_early = atoi(e) != 0;
+  if (const char* e = CDA_AB_ENV("CDA_L1_QUADS")) c->l1_quads = atoi(e) != 0;
   if (const char* e = CDA_AB_ENV("CDA_STAGING")) c->staging = atoi(e) & 3;
   if (const char* e = CDA_AB_ENV("CDA_CONSENSUS")) c->consensus = atoi(e) != 0;
   // the one-block path's A/B forms and the huge-page opt-in (test builds only, CDA_AB_ENV): read here once, never per

@@ -1,6 +1,7 @@
 // nmt_dev.h — device building blocks of the NMT and RFC-6962 hash kernels (nmt_kernels.hip, split_kernels.hip,
-// inclusion_kernels.hip): the leaf message and record, the inner node in its three forms, 96-B records to and from
-// registers, the push-order compare, RFC-6962 digests and levels, and the level loops several kernels share.
+// inclusion_kernels.hip): the leaf message and record, the inner node in its three forms and level 1 by 2x2 cell quads
+// in two, 96-B records to and from registers, the push-order compare, RFC-6962 digests and levels, and the level loops
+// several kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -260,6 +261,52 @@ __device__ __forceinline__ void node_record(const uint32_t* L, const uint32_t* R
   rec_digest_words(S[14], st, o);
 }
 
+// Message blocks 0..2 of an inner node, 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits) (48 words), from the
+// child records in memory.  Block 0 takes a laundered pointer; blocks 1 and 2 launder theirs after `after` (a word of
+// the previous compression's state), see hash_node_mem.  ns_lds (optional): the first 64 B of L (block 0) / R (block
+// 1) are parked there.
+__device__ __forceinline__ void node_mem_block0(const uint4* pl, uint32_t (&m)[16], uint4* ns_lds = nullptr) {
+  // words 0..15 <- L words 0..15
+  uint32_t L[16];
+  load16(pl, L);
+  m[0] = be_window(0x01000000u, L[0], 3);
+#pragma unroll
+  for (int i = 1; i < 16; i++) m[i] = be_window(L[i - 1], L[i], 3);
+  if (ns_lds)
+#pragma unroll
+    for (int i = 0; i < 4; i++) ns_lds[i] = make_uint4(L[4 * i], L[4 * i + 1], L[4 * i + 2], L[4 * i + 3]);
+}
+__device__ __forceinline__ void node_mem_block1(const uint4* pl, const uint4* pr, uint32_t after, uint32_t (&m)[16],
+                                                uint4* ns_lds = nullptr) {
+  // words 16..31 <- L words 15..22, R words 0..8
+  uint32_t L[16], R[16];  // L words 12..27, R words 0..15
+  load16(launder_after(pl, after) + 3, L);  // words 12..27: only 12..23 are read
+  load16(launder_after(pr, after), R);      // words 0..15: only 0..11 are read
+  if (ns_lds)
+#pragma unroll
+    for (int i = 0; i < 4; i++) ns_lds[4 + i] = make_uint4(R[4 * i], R[4 * i + 1], R[4 * i + 2], R[4 * i + 3]);
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const int wi = 16 + i;
+    if (wi <= 21) m[i] = be_window(L[wi - 13], L[wi - 12], 3);
+    else if (wi == 22) m[i] = be_window(L[9], L[10], 3) | (R[0] & 0xFFu);
+    else m[i] = be_window(R[wi - 23], R[wi - 22], 1);
+  }
+}
+__device__ __forceinline__ void node_mem_block2(const uint4* pr, uint32_t after, uint32_t (&m)[16]) {
+  // words 32..47 <- R words 8..23
+  uint32_t R[16];
+  load16(launder_after(pr, after) + 2, R);
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const int wi = 32 + i;
+    if (wi <= 44) m[i] = be_window(R[wi - 31], R[wi - 30], 1);
+    else if (wi == 45) m[i] = be_window(R[14], R[15], 1) | 0x00800000u;
+    else if (wi == 46) m[i] = 0;
+    else m[i] = 181u * 8u;
+  }
+}
+
 // Inner node from the two child records at pl / pr, written to po (po may equal
 // pl: every read precedes the stores).  The children are read block by block
 // through laundered pointers ordered after the previous compression, so the
@@ -276,46 +323,11 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
                                               uint4* ns_lds = nullptr) {
   uint32_t st[8], m[16];
   sha256_init(st);
-  // message = 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits); 48 words
-  {  // block 0: words 0..15 <- L words 0..15
-    uint32_t L[16];
-    load16(launder(pl), L);
-    m[0] = be_window(0x01000000u, L[0], 3);
-#pragma unroll
-    for (int i = 1; i < 16; i++) m[i] = be_window(L[i - 1], L[i], 3);
-    if (ns_lds)
-#pragma unroll
-      for (int i = 0; i < 4; i++) ns_lds[i] = make_uint4(L[4 * i], L[4 * i + 1], L[4 * i + 2], L[4 * i + 3]);
-  }
+  node_mem_block0(launder(pl), m, ns_lds);
   sha256_compress_fenced(st, m);
-  {  // block 1: words 16..31 <- L words 15..22, R words 0..8
-    uint32_t L[16], R[16];  // L words 12..27, R words 0..15
-    load16(launder_after(pl, st[0]) + 3, L);  // words 12..27: only 12..23 are read
-    load16(launder_after(pr, st[0]), R);      // words 0..15: only 0..11 are read
-    if (ns_lds)
-#pragma unroll
-      for (int i = 0; i < 4; i++) ns_lds[4 + i] = make_uint4(R[4 * i], R[4 * i + 1], R[4 * i + 2], R[4 * i + 3]);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int wi = 16 + i;
-      if (wi <= 21) m[i] = be_window(L[wi - 13], L[wi - 12], 3);
-      else if (wi == 22) m[i] = be_window(L[9], L[10], 3) | (R[0] & 0xFFu);
-      else m[i] = be_window(R[wi - 23], R[wi - 22], 1);
-    }
-  }
+  node_mem_block1(pl, pr, st[0], m, ns_lds);
   sha256_compress_fenced(st, m);
-  {  // block 2: words 32..47 <- R words 8..23
-    uint32_t R[16];
-    load16(launder_after(pr, st[0]) + 2, R);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int wi = 32 + i;
-      if (wi <= 44) m[i] = be_window(R[wi - 31], R[wi - 30], 1);
-      else if (wi == 45) m[i] = be_window(R[14], R[15], 1) | 0x00800000u;
-      else if (wi == 46) m[i] = 0;
-      else m[i] = 181u * 8u;
-    }
-  }
+  node_mem_block2(pr, st[0], m);
   sha256_compress_fenced(st, m);
 
   // the namespace range comes from the children's first 16 words, read again
@@ -348,49 +360,47 @@ __device__ __forceinline__ void hash_node_mem(const uint4* pl, const uint4* pr, 
 // Records as pl / pr / po of hash_node_mem (po may equal pl).
 constexpr uint32_t kParityMid14[8] = {0xa8abd42b, 0x092979bd, 0x8d5926ca, 0x8df58526,
                                       0xa812caa9, 0x7cc8da5d, 0x33a85111, 0x7d669380};
-__device__ __forceinline__ void hash_node_parity(const uint4* pl, const uint4* pr, uint4* po, bool store = true) {
-  uint32_t st[8], m[16];
-  sha256_init(st);
-  // the words are read block by block, each load ordered after the previous compression (as in hash_node_mem)
-  uint32_t L[12];  // L words 12..23: 13..22 are read
-  {  // block 0: 0x01 ‖ 0xFF x 58 ‖ L digest bytes 0..4
-    const uint4 v = launder(pl)[3];
-    L[3] = v.w;
-    m[0] = 0x01FFFFFFu;
+// Message blocks of a parity node; pointers and `after` as in node_mem_block*.  Block 0 returns L word 15 (loaded with
+// it) for block 1.
+__device__ __forceinline__ uint32_t parity_block0(const uint4* pl, uint32_t (&m)[16]) {
+  // 0x01 ‖ 0xFF x 58 ‖ L digest bytes 0..4
+  const uint4 v = pl[3];
+  m[0] = 0x01FFFFFFu;
 #pragma unroll
-    for (int i = 1; i < 14; i++) m[i] = 0xFFFFFFFFu;
-    m[14] = be_window(v.y, v.z, 3);
-    m[15] = be_window(v.z, v.w, 3);
-    uint32_t mid[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) mid[i] = kParityMid14[i];
-    sha256_compress_fenced_from<14>(st, mid, m);
-  }
+  for (int i = 1; i < 14; i++) m[i] = 0xFFFFFFFFu;
+  m[14] = be_window(v.y, v.z, 3);
+  m[15] = be_window(v.z, v.w, 3);
+  return v.w;
+}
+__device__ __forceinline__ void parity_block1(const uint4* pl, uint32_t after, uint32_t l15, uint32_t (&m)[16]) {
+  uint32_t L[12];  // L words 12..23: 15..22 are read
+  L[3] = l15;
   {
-    const uint4* p = launder_after(pl, st[0]) + 3;
+    const uint4* p = launder_after(pl, after) + 3;
 #pragma unroll
     for (int i = 1; i < 3; i++) {
       const uint4 v = p[i];
       L[4 * i] = v.x, L[4 * i + 1] = v.y, L[4 * i + 2] = v.z, L[4 * i + 3] = v.w;
     }
   }
-  // block 1: L digest bytes 5..31 ‖ R's 0xFF x 37
+  // L digest bytes 5..31 ‖ R's 0xFF x 37
 #pragma unroll
   for (int i = 0; i < 6; i++) m[i] = be_window(L[3 + i], L[4 + i], 3);  // words 16..21 <- L words 15..21
   m[6] = be_window(L[9], L[10], 3) | 0xFFu;                              // word 22: L bytes 87..89, R byte 0
 #pragma unroll
   for (int i = 7; i < 16; i++) m[i] = 0xFFFFFFFFu;
-  sha256_compress_fenced(st, m);
+}
+__device__ __forceinline__ void parity_block2(const uint4* pr, uint32_t after, uint32_t (&m)[16]) {
   uint32_t R[12];  // R words 12..23: 14..23 are read
   {
-    const uint4* p = launder_after(pr, st[0]) + 3;
+    const uint4* p = launder_after(pr, after) + 3;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       const uint4 v = p[i];
       R[4 * i] = v.x, R[4 * i + 1] = v.y, R[4 * i + 2] = v.z, R[4 * i + 3] = v.w;
     }
   }
-  // block 2: R's 0xFF x 21 ‖ R digest ‖ 0x80 ‖ 0.. ‖ len
+  // R's 0xFF x 21 ‖ R digest ‖ 0x80 ‖ 0.. ‖ len
 #pragma unroll
   for (int i = 0; i < 5; i++) m[i] = 0xFFFFFFFFu;
 #pragma unroll
@@ -398,12 +408,146 @@ __device__ __forceinline__ void hash_node_parity(const uint4* pl, const uint4* p
   m[13] = be_window(R[10], R[11], 1) | 0x00800000u;
   m[14] = 0;
   m[15] = 181u * 8u;
-  sha256_compress_fenced(st, m);
-  uint32_t o[24];
+}
+// Block 0 of a parity node into the initial state st, from kParityMid14
+__device__ __forceinline__ uint32_t parity_compress_block0(const uint4* pl, uint32_t (&st)[8], uint32_t (&m)[16]) {
+  sha256_init(st);
+  const uint32_t l15 = parity_block0(pl, m);
+  uint32_t mid[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) mid[i] = kParityMid14[i];
+  sha256_compress_fenced_from<14>(st, mid, m);
+  return l15;
+}
+// The record of a parity node: 0xFF x 58 ‖ digest ‖ 6 zero bytes
+__device__ __forceinline__ void parity_record(const uint32_t* st, uint32_t (&o)[24]) {
 #pragma unroll
   for (int i = 0; i < 14; i++) o[i] = 0xFFFFFFFFu;
   rec_digest_words(0xFFFFu, st, o);
+}
+__device__ __forceinline__ void hash_node_parity(const uint4* pl, const uint4* pr, uint4* po, bool store = true) {
+  uint32_t st[8], m[16];
+  // the words are read block by block, each load ordered after the previous compression (as in hash_node_mem)
+  const uint32_t l15 = parity_compress_block0(launder(pl), st, m);
+  parity_block1(pl, st[0], l15, m);
+  sha256_compress_fenced(st, m);
+  parity_block2(pr, st[0], m);
+  sha256_compress_fenced(st, m);
+  uint32_t o[24];
+  parity_record(st, o);
   if (store) store_rec(po, o);
+}
+
+// ---------------------------------------------------------------------------
+// Level 1 by 2x2 cell quads.  The cells TL, TR / BL, BR at rows 2R, 2R+1 and columns 2C, 2C+1 have four level-1
+// parents: row-top (TL, TR), row-bottom (BL, BR), col-left (TL, BL), col-right (TR, BR).  Row-top and col-left share
+// their left child, so block 0 (0x01 ‖ L[0..63), left child only) is the same compression from the same IV; in a
+// parity quad block 1 (L digest tail ‖ 0xFF x 37) is too.  Row-bottom and col-right share their right child, so block
+// 2 (R[37..90) ‖ pad) is one message into two chaining states: one schedule, two round chains
+// (sha256_compress_fenced_2s).  Children are read piecewise through laundered pointers ordered after the previous
+// compression, as in the node forms above.  Records and their bytes are those of hash_node_mem / hash_node_parity.
+// The two nodes of a pair run the same blocks on other children, so each pair is a loop of two trips over one copy of
+// the code (18.2 k instead of 27.5 k VALU instructions in nmt_level1_quads_kernel; measured no slower than unrolled,
+// DESIGN.md §21); the states the shared block 2 needs leave the loop through statically indexed copies.
+// ---------------------------------------------------------------------------
+// The record of the node with children pl / pr and final state st, to po: the namespace range from the children's
+// first 16 words, read (again) after `after`
+__device__ __forceinline__ void node_record_mem(const uint4* pl, const uint4* pr, uint32_t after, const uint32_t* stp,
+                                                uint4* po) {
+  uint32_t L[16], R[16], st[8], o[24];
+#pragma unroll
+  for (int i = 0; i < 8; i++) st[i] = stp[i];
+  load16(launder_after(pl, after), L);
+  load16(launder_after(pr, after), R);
+  node_record(L, R, st, o);
+  store_rec(po, o);
+}
+// General form: valid for any quad.
+__device__ __forceinline__ void hash_quad_mem(const uint4* tl, const uint4* tr, const uint4* bl, const uint4* br,
+                                              uint4* row_top, uint4* row_bot, uint4* col_left, uint4* col_right) {
+  uint32_t s0[8], st[8], m[16];
+  sha256_init(s0);
+  node_mem_block0(launder(tl), m);  // block 0 of TL, once for row-top and col-left
+  sha256_compress_fenced(s0, m);
+  uint32_t after = s0[0];
+#pragma unroll 1
+  for (int n = 0; n < 2; n++) {  // row-top (TL, TR), then col-left (TL, BL), both from s0
+    const uint4* pr = n == 0 ? tr : bl;
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = s0[i];
+    node_mem_block1(tl, pr, after, m);
+    sha256_compress_fenced(st, m);
+    node_mem_block2(pr, st[0], m);
+    sha256_compress_fenced(st, m);
+    node_record_mem(tl, pr, st[0], st, n == 0 ? row_top : col_left);
+    after = st[0];
+  }
+  uint32_t S[2][8];  // row-bottom (BL, BR), col-right (TR, BR): blocks 0 and 1 each, block 2 with one schedule
+#pragma unroll 1
+  for (int n = 0; n < 2; n++) {
+    const uint4* pl = n == 0 ? bl : tr;
+    sha256_init(st);
+    node_mem_block0(launder_after(pl, after), m);
+    sha256_compress_fenced(st, m);
+    node_mem_block1(pl, br, st[0], m);
+    sha256_compress_fenced(st, m);
+    after = st[0];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {  // S[n] would be a runtime index: scratch
+      if (n == 0) S[0][i] = st[i];
+      else S[1][i] = st[i];
+    }
+  }
+  node_mem_block2(br, after, m);
+  sha256_compress_fenced_2s(S, m);
+  node_record_mem(bl, br, S[1][0], S[0], row_bot);
+  node_record_mem(tr, br, S[1][0], S[1], col_right);
+}
+// Parity form: every cell of the quad is a parity leaf (whole waves only, as hash_node_parity).  Blocks 0 and 1 of TL
+// once; block 2 of row-top (TR) and col-left (BL) are two messages from that one state.
+__device__ __forceinline__ void hash_quad_parity(const uint4* tl, const uint4* tr, const uint4* bl, const uint4* br,
+                                                 uint4* row_top, uint4* row_bot, uint4* col_left, uint4* col_right) {
+  uint32_t S[2][8], m[16], o[24];
+  uint32_t after;
+  {
+    uint32_t s1[8], st[8];
+    const uint32_t l15 = parity_compress_block0(launder(tl), s1, m);
+    parity_block1(tl, s1[0], l15, m);
+    sha256_compress_fenced(s1, m);
+    after = s1[0];
+    // one after the other, not sha256_compress_n<2, 8>: with two schedules in registers the kernel spilled 44 VGPRs
+    // at 128, and at 4 waves per SIMD the second chain's instruction-level parallelism buys nothing
+#pragma unroll 1
+    for (int n = 0; n < 2; n++) {  // row-top (TR), then col-left (BL)
+#pragma unroll
+      for (int i = 0; i < 8; i++) st[i] = s1[i];
+      parity_block2(n == 0 ? tr : bl, after, m);
+      sha256_compress_fenced(st, m);
+      parity_record(st, o);
+      store_rec(n == 0 ? row_top : col_left, o);
+      after = st[0];
+    }
+  }
+#pragma unroll 1
+  for (int n = 0; n < 2; n++) {  // row-bottom (BL, BR), col-right (TR, BR)
+    const uint4* pl = n == 0 ? bl : tr;
+    uint32_t st[8];
+    const uint32_t l15 = parity_compress_block0(launder_after(pl, after), st, m);
+    parity_block1(pl, st[0], l15, m);
+    sha256_compress_fenced(st, m);
+    after = st[0];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      if (n == 0) S[0][i] = st[i];
+      else S[1][i] = st[i];
+    }
+  }
+  parity_block2(br, after, m);
+  sha256_compress_fenced_2s(S, m);
+  parity_record(S[0], o);
+  store_rec(row_bot, o);
+  parity_record(S[1], o);
+  store_rec(col_right, o);
 }
 
 // Message block B (0..2) of an inner node: 0x01 ‖ L[0..90) ‖ R[0..90) ‖ 0x80 ‖ 0.. ‖ len(1448 bits), children in

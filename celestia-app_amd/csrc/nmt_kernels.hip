@@ -160,10 +160,40 @@ nmt_levels_kernel(LevelSet ls, int log2w, int log2n_out, int M, uint32_t total) 
   }
 }
 
+// Level 1 of the row and the column trees of a batch from 2x2 cell quads (nmt_dev.h): one thread per quad (R, C) of a
+// block, C fastest, then R, then the block.  It hashes the four level-1 parents of cells (2R, 2C) .. (2R + 1, 2C + 1):
+// nodes C of row trees 2R and 2R + 1, nodes R of column trees 2C and 2C + 1 (adjacent records in the node-major
+// column layout), into the level-1 buffer d1 describes.  A quad is parity iff 2R >= k or 2C >= k (k even); a wave
+// takes the parity form only when all its quads are parity, the general form otherwise (valid for parity nodes too).
+// At k >= 128 a wave is 64 quads of one quad-row, all left half or all right half: both forms run wave-uniform.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+nmt_level1_quads_kernel(const uint4* __restrict__ leaves, LevelDesc d1, int log2w, uint32_t total) {
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= total) return;
+  const int log2k = log2w - 1;
+  const unsigned w = 1u << log2w, k = w >> 1;
+  const unsigned C = gid & (k - 1), R = (gid >> log2k) & (k - 1), b = gid >> (2 * log2k);
+  const uint4* tl = leaves + (((size_t)b << (2 * log2w)) + ((size_t)(2 * R) << log2w) + 2 * C) * 6;
+  const uint4 *tr = tl + 6, *bl = tl + (size_t)w * 6, *br = bl + 6;
+  uint4* row_top = level_rec(d1, b, false, 2 * R, C);
+  uint4* row_bot = level_rec(d1, b, false, 2 * R + 1, C);
+  uint4* col_left = level_rec(d1, b, true, 2 * C, R);
+  uint4* col_right = level_rec(d1, b, true, 2 * C + 1, R);
+#if CDA_NO_PARITY_MID  // diagnostic A/B, as in nmt_levels_kernel
+  const bool parity = false;
+#else
+  const bool parity = 2 * R >= k || 2 * C >= k;
+#endif
+  if (__all(parity)) hash_quad_parity(tl, tr, bl, br, row_top, row_bot, col_left, col_right);
+  else hash_quad_mem(tl, tr, bl, br, row_top, row_bot, col_left, col_right);
+}
+
 // Leaf records -> roots of all 4k trees of nblocks blocks.  d_levels holds the inner levels
-// (2w x (w - 2) records per block at most); M = 2 levels per launch (the last launch may take 1 or 3).
+// (2w x (w - 2) records per block at most).  Trees of at least 4 leaves: level 1 from the quad kernel and level 2 from
+// one nmt_levels_kernel launch (both in the profiling scope nmt_levels_1), then M = 2 levels per launch (the last
+// launch may take 1 or 3).  Trees of 2 leaves: the one nmt_levels_kernel launch.
 int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k, int nblocks, hipStream_t s,
-                     void* prof_ctx) {
+                     void* prof_ctx, bool l1_quads) {
   const int w = 2 * k;
   if (k < 1) return -2;
   const int L = ilog2i(w);
@@ -186,14 +216,28 @@ int launch_nmt_trees(const void* d_leaves, void* d_levels, void* d_roots, int k,
     }
     return d;
   };
-  for (int l_in = 0; l_in < L;) {
-    const auto [M, log2n_out] = subtree_launch(L, l_in);
+  auto levels = [&](int l_in, int M) {  // levels l_in + 1 .. l_in + M in one nmt_levels_kernel launch
+    const int log2n_out = L - l_in - M;
     LevelSet ls{};
     for (int q = 0; q <= M; q++) ls.lv[q] = desc(l_in + q);
     const uint32_t total = (uint32_t)nblocks * 2u * ((uint32_t)w << log2n_out);
+    hipLaunchKernelGGL(nmt_levels_kernel, dim3((total + 255) / 256), dim3(256), 0, s, ls, L, log2n_out, M, total);
+  };
+  int l_in = 0;
+  if (L >= 2 && l1_quads) {
+    ProfScope ps(prof_ctx, "nmt_levels_1", s);
+    const uint32_t total = (uint32_t)nblocks * (uint32_t)k * (uint32_t)k;
+    hipLaunchKernelGGL(nmt_level1_quads_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const uint4*)d_leaves,
+                       desc(1), L, total);
+    levels(1, 1);
+    l_in = 2;
+  }
+  if (hipGetLastError() != hipSuccess) return -1;
+  while (l_in < L) {
+    const int M = subtree_launch(L, l_in).M;
     {
       ProfScope ps(prof_ctx, l_in == 0 ? "nmt_levels_1" : "nmt_levels", s);
-      hipLaunchKernelGGL(nmt_levels_kernel, dim3((total + 255) / 256), dim3(256), 0, s, ls, L, log2n_out, M, total);
+      levels(l_in, M);
     }
     if (hipGetLastError() != hipSuccess) return -1;
     l_in += M;

@@ -182,6 +182,29 @@ __device__ __forceinline__ void sha256_compress_fenced(uint32_t s[8], const uint
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// One 16-word block compressed into two chaining states (w is clobbered): the message schedule does not depend on the
+// state, so it is expanded once and both round chains consume each word, round-interleaved as in sha256_compress_n
+// (which is the other pairing: N messages, each with its own schedule).  64 rounds x 2 + one schedule instead of two of
+// each.  Fenced like sha256_compress_fenced: every 8 rounds and after the block.
+__device__ __forceinline__ void sha256_compress_fenced_2s(uint32_t (&s)[2][8], uint32_t (&w)[16]) {
+  uint32_t a[2], b[2], c[2], d[2], e[2], f[2], g[2], h[2];
+#pragma unroll
+  for (int n = 0; n < 2; n++) {
+    a[n] = s[n][0]; b[n] = s[n][1]; c[n] = s[n][2]; d[n] = s[n][3];
+    e[n] = s[n][4]; f[n] = s[n][5]; g[n] = s[n][6]; h[n] = s[n][7];
+  }
+#pragma unroll
+  for (int t = 0; t < 64; t++) {
+    const uint32_t wt = sha256_sched(w, t);
+#pragma unroll
+    for (int n = 0; n < 2; n++) sha256_round(a[n], b[n], c[n], d[n], e[n], f[n], g[n], h[n], K256::v[t], wt);
+    if ((t % 8) == 7) __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int n = 0; n < 2; n++) sha256_add(s[n], a[n], b[n], c[n], d[n], e[n], f[n], g[n], h[n]);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 // A block whose first START message words are the constants w[0..START) and whose chaining input is s: the 64-round
 // compression started from `mid`, the working state after rounds 0..START-1 (precomputed on the host for the fixed
 // prefix).  The schedule still reads w[0..16) (the constant words fold into it).  s += the final working state.
