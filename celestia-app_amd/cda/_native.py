@@ -60,6 +60,7 @@ EXPORTS = [
     "cda_square_share_proofs", "cda_share_proofs_validate", "cda_share_proofs_validate_device",
     "cda_square_prove_namespace", "cda_nmt_verify_namespace", "cda_nmt_verify_namespace_device",
     "cda_square_open_eds", "cda_befp_validate", "cda_befp_validate_device",
+    "cda_samples_assemble_device", "cda_square_open_eds_device", "cda_square_rebuild",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -148,6 +149,16 @@ class BefpEntry(ctypes.Structure):
 # cda_befp_validate's verdicts (include/cda.h CDA_BEFP_*)
 BEFP_FRAUD, BEFP_NO_FRAUD, BEFP_MALFORMED, BEFP_TOO_FEW, BEFP_BAD_SHARE = 1, 0, -1, -2, -3
 
+
+class SampleDesc(ctypes.Structure):
+    """cda_sample_desc: one proved cell of a cda_square_rebuild / cda_samples_assemble_device batch."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("pos", ctypes.c_uint32),
+                ("node_off", ctypes.c_uint32), ("nnodes", ctypes.c_uint32)]
+
+
+# the per-sample statuses of an assembled square (include/cda.h CDA_SAMPLE_*)
+SAMPLE_PLACED, SAMPLE_DUPLICATE, SAMPLE_CONFLICT, SAMPLE_REJECTED, SAMPLE_MALFORMED = range(5)
+
 # cda_namespace_result.kind (include/cda.h CDA_NSP_*), and "no leaf hash" of a cda_nmt_ns_proof_desc
 NSP_EMPTY, NSP_INCLUSION, NSP_ABSENCE = range(3)
 NO_LEAF_HASH = 0xFFFFFFFF
@@ -173,6 +184,8 @@ NMT_NS_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off
 BEFP_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("entry_off", "<u4"), ("nshares", "<u4"),
                             ("root_off", "<u4")])
 BEFP_ENTRY_DTYPE = np.dtype([("pos", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4")])
+SAMPLE_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("pos", "<u4"), ("node_off", "<u4"),
+                              ("nnodes", "<u4")])
 RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
 NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("leaf_off", "<u4"), ("root", "<u4")])
@@ -263,6 +276,9 @@ def lib(path=None):
                 "cda_square_open_eds": (I32, [P, U32, P, ctypes.POINTER(P), P, P, P, P]),
                 "cda_befp_validate": (I32, [P, U32, U32, P, P, U32, P, P, U32, P, U32, P]),
                 "cda_befp_validate_device": (I32, [P, U32, U32, P, P, U32, P, P, U32, P, U32, P, P]),
+                "cda_samples_assemble_device": (I32, [P, U32, U32, P, P, P, U32, P, P, P, P, P]),
+                "cda_square_open_eds_device": (I32, [P, U32, P, ctypes.POINTER(P), P, P, P, P, P]),
+                "cda_square_rebuild": (I32, [P, U32, U32, P, P, P, U32, P, P, ctypes.POINTER(P), P, P, P, P, P]),
             }
             for name, (res, args) in sig.items():
                 f = getattr(L, name)
@@ -716,6 +732,65 @@ class Context:
                                               V(d_nodes), nnodes, V(d_roots), nroots, V(d_verdicts), V(stream or 0))
         _check(rc, ctx=self)
 
+    # ---- a square rebuilt from proved samples ----
+    def samples_assemble_device(self, k, nsamples, d_descs, d_shares, d_nodes, nnodes, d_roots, d_eds, d_present,
+                                d_statuses, stream=None):
+        """cda_samples_assemble_device: verify the samples and place the accepted cells, every argument a device
+        address, asynchronous on `stream`.  d_eds ((2k)^2 x 512 B), d_present ((2k)^2) and d_statuses (nsamples,
+        SAMPLE_* codes) are the outputs."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_samples_assemble_device(self._h, k, nsamples, V(d_descs), V(d_shares), V(d_nodes), nnodes,
+                                                 V(d_roots), V(d_eds), V(d_present), V(d_statuses), V(stream or 0))
+        _check(rc, ctx=self)
+
+    def open_square_eds_device(self, k, d_eds, stream=None):
+        """cda_square_open_eds_device: retain the extended square at device address d_eds ((2k)^2 x 512 B) as
+        open_square_eds retains one from host memory.  -> Square."""
+        w = 2 * k
+        row_roots, col_roots = np.empty((w, NODE_SIZE), np.uint8), np.empty((w, NODE_SIZE), np.uint8)
+        dah = np.empty(32, np.uint8)
+        h, err = ctypes.c_void_p(), ErrInfo()
+        rc = self._L.cda_square_open_eds_device(self._h, k, ctypes.c_void_p(d_eds), ctypes.byref(h), _p(row_roots),
+                                                _p(col_roots), _p(dah), ctypes.byref(err),
+                                                ctypes.c_void_p(stream or 0))
+        _check(rc, err, self)
+        return Square._adopt(self, k, h, row_roots, col_roots, dah)
+
+    def rebuild_square_status(self, descs, shares, nodes, row_roots, col_roots, want_eds=False):
+        """cda_square_rebuild without raising on the two repair errors: (rc, square or None, statuses, present, eds or
+        None, err).  On CDA_E_UNREPAIRABLE / CDA_E_BYZANTINE present and eds hold the square where rsmt2d stops."""
+        descs = np.ascontiguousarray(descs, SAMPLE_DESC_DTYPE)
+        n = len(descs)
+        shares = np.ascontiguousarray(shares, np.uint8).reshape(n, SHARE_SIZE)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        row_roots = np.ascontiguousarray(row_roots, np.uint8).reshape(-1, NODE_SIZE)
+        col_roots = np.ascontiguousarray(col_roots, np.uint8).reshape(-1, NODE_SIZE)
+        w = len(row_roots)
+        if len(col_roots) != w or w % 2:
+            raise CdaError(E_ARG, "the roots are 2k row roots and 2k column roots")
+        statuses = np.full(n, SAMPLE_MALFORMED, np.uint8)
+        present = np.zeros(w * w, np.uint8)
+        eds = np.zeros((w * w, SHARE_SIZE), np.uint8) if want_eds else None
+        dah = np.empty(32, np.uint8)
+        h, err = ctypes.c_void_p(), ErrInfo()
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_square_rebuild(self._h, w // 2, n, p(descs), p(shares), p(nodes), len(nodes), _p(row_roots),
+                                        _p(col_roots), ctypes.byref(h), p(statuses), _p(present), _p(eds), _p(dah),
+                                        ctypes.byref(err))
+        if rc not in (OK, E_UNREPAIRABLE, E_BYZANTINE):
+            _check(rc, err, self)
+        sq = Square._adopt(self, w // 2, h, row_roots.copy(), col_roots.copy(), dah) if rc == OK else None
+        return rc, sq, statuses, present, eds, err
+
+    def rebuild_square(self, descs, shares, nodes, row_roots, col_roots):
+        """cda_square_rebuild: the samples (SAMPLE_DESC_DTYPE rows, shares (n, 512), nodes (m, 90)) verified, placed,
+        repaired against the roots and retained.  -> Square; CdaError (axis, index) when rsmt2d's Repair fails."""
+        rc, sq, _, _, _, err = self.rebuild_square_status(descs, shares, nodes, row_roots, col_roots)
+        _check(rc, err, self)
+        return sq
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -764,6 +839,15 @@ class Square:
         self._h = h
         self.dah = dah.tobytes()
         self.max_nodes = 2 * (w.bit_length() - 1)
+
+    @classmethod
+    def _adopt(cls, ctx, k, handle, row_roots, col_roots, dah):
+        """The Square of a handle the library has already built (open_square_eds_device, rebuild_square)."""
+        self = object.__new__(cls)
+        self._ctx, self._h, self.k = ctx, handle, k
+        self.row_roots, self.col_roots, self.dah = row_roots, col_roots, dah.tobytes()
+        self.max_nodes = 2 * ((2 * k).bit_length() - 1)
+        return self
 
     def prove(self, queries, want_shares=True):
         """cda_square_prove.  queries: (axis, index, start, end) tuples or RANGE_QUERY_DTYPE rows.

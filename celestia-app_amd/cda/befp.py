@@ -9,6 +9,7 @@ the rule below (B1-B4) is this project's statement of it; the messa
 follow the spec and rsmt2d.
 
     create(square, axis, index)           the producer, for a node that holds the committed square (open_square_eds)
+    from_samples(samples, axis, index, k) the producer, for a node that holds proved samples (cda.sampling.rebuild)
     validate_host(proof, rows, cols)      B1-B4 on the host (hashlib), the mirror the device form is tested against
     validate(ctx, proofs, roots)          cda_befp_validate: the whole batch in one call
 """
@@ -47,6 +48,21 @@ def create(square, axis, index, positions=None):
                             [(pos, cells[i].tobytes(),
                               NMTProof(index, index + 1, [nodes[i, j].tobytes() for j in range(counts[i])]))
                              for i, pos in enumerate(positions)])
+
+
+def from_samples(samples, axis, index, k):
+    """The BEFP of axis (axis, index) of a 2k x 2k square out of samples a node already holds ((axis, index, pos,
+    share, NMTProof) tuples, cda.sampling): those cells of the axis that were proved in their ORTHOGONAL trees, in
+    increasing position, the first sample of a position standing for it.  -> BadEncodingProof, or None when fewer than
+    k positions are covered (B2 would say TOO_FEW).  Nothing is verified here: validate does that."""
+    by_pos = {}
+    for s_axis, s_index, s_pos, share, nmt in samples:
+        # leaf `index` of the orthogonal tree s_index is cell s_index of the axis
+        if s_axis == 1 - axis and s_pos == index and 0 <= s_index < 2 * k:
+            by_pos.setdefault(int(s_index), (bytes(share), nmt))
+    if len(by_pos) < k:
+        return None
+    return BadEncodingProof(int(axis), int(index), [(pos,) + by_pos[pos] for pos in sorted(by_pos)])
 
 
 def _orthogonal_root(proof, pos, row_roots, col_roots):

@@ -69,3 +69,73 @@ def verify_samples(ctx, samples, row_roots, col_roots):
     descs, namespaces, nodes, leaves = pack_samples(samples, k)
     ok = ctx.nmt_verify(descs, namespaces, np.concatenate([row_roots, col_roots]), nodes, leaves)
     return [bool(x) for x in ok]
+
+
+# ---- a square rebuilt from proved samples: place, repair, retain ----
+PLACED, DUPLICATE, CONFLICT, REJECTED, MALFORMED = (N.SAMPLE_PLACED, N.SAMPLE_DUPLICATE, N.SAMPLE_CONFLICT,
+                                                    N.SAMPLE_REJECTED, N.SAMPLE_MALFORMED)
+
+
+def pack_sample_descs(samples):
+    """The arrays cda_square_rebuild takes for `samples` ((axis, index, pos, share, NMTProof) tuples):
+    (descs, shares, nodes).  Only the proof's nodes are used: the leaf is [pos, pos + 1) by the rule."""
+    n = len(samples)
+    descs = np.zeros(n, N.SAMPLE_DESC_DTYPE)
+    shares = np.zeros((n, N.SHARE_SIZE), np.uint8)
+    nodes = []
+    for i, (axis, index, pos, share, proof) in enumerate(samples):
+        if len(share) != N.SHARE_SIZE or any(len(x) != N.NODE_SIZE for x in proof.nodes):
+            raise ValueError("a sample is one 512-byte cell with a proof in 90-byte nodes")
+        descs[i] = (axis, index, pos, len(nodes), len(proof.nodes))
+        shares[i] = np.frombuffer(bytes(share), np.uint8)
+        nodes += [bytes(x) for x in proof.nodes]
+    nodes = np.frombuffer(b"".join(nodes), np.uint8).reshape(-1, N.NODE_SIZE) if nodes else \
+        np.zeros((0, N.NODE_SIZE), np.uint8)
+    return descs, shares, nodes
+
+
+def assemble_host(samples, row_roots, col_roots):
+    """The placement rule (csrc/sample_place_rule.h) on the host, the mirror cda_samples_assemble_device is tested
+    against: every sample is verified with NMTProof.verify_inclusion under the namespace of sample_namespace; the
+    lowest-indexed verified sample of a cell is PLACED, every later verified one DUPLICATE or CONFLICT by its bytes.
+    -> (eds ((2k)^2, 512) uint8, zero where nothing is placed; present ((2k)^2,) uint8; statuses (n,) uint8)."""
+    w = len(row_roots)
+    k = w // 2
+    eds = np.zeros((w * w, N.SHARE_SIZE), np.uint8)
+    present = np.zeros(w * w, np.uint8)
+    statuses = np.zeros(len(samples), np.uint8)
+    placed = {}
+    for p, (axis, index, pos, share, proof) in enumerate(samples):
+        if axis not in (0, 1) or not 0 <= index < w or not 0 <= pos < w:
+            statuses[p] = MALFORMED
+            continue
+        share = bytes(share)
+        root = bytes(col_roots[index]) if axis else bytes(row_roots[index])
+        ns = sample_namespace(k, axis, index, pos, share)
+        # the range is the rule's, not the message's: only the nodes of the carried proof are used
+        if not NMTProof(pos, pos + 1, list(proof.nodes)).verify_inclusion(ns, [share], root):
+            statuses[p] = REJECTED
+            continue
+        cell = pos * w + index if axis else index * w + pos
+        if cell not in placed:
+            placed[cell] = share
+            eds[cell] = np.frombuffer(share, np.uint8)
+            present[cell] = 1
+            statuses[p] = PLACED
+        else:
+            statuses[p] = DUPLICATE if placed[cell] == share else CONFLICT
+    return eds, present, statuses
+
+
+def rebuild(ctx, samples, row_roots, col_roots, want_eds=False):
+    """cda_square_rebuild over `samples`: verified, placed, repaired against the roots (rsmt2d Repair) and retained,
+    without the square leaving the device.  -> (Square, statuses, present[, eds]).  When Repair fails CdaError carries
+    the code (E_UNREPAIRABLE, E_BYZANTINE with axis and index) and, as attributes, statuses, present and eds."""
+    descs, shares, nodes = pack_sample_descs(samples)
+    rc, sq, statuses, present, eds, err = ctx.rebuild_square_status(descs, shares, nodes, row_roots, col_roots,
+                                                                    want_eds)
+    if rc != N.OK:
+        e = N.CdaError(rc, axis=err.axis, index=err.index)
+        e.statuses, e.present, e.eds = statuses, present, eds
+        raise e
+    return (sq, statuses, present, eds) if want_eds else (sq, statuses, present)

@@ -151,6 +151,10 @@ void set_err(cda_err_info* e, int code, int axis, int index, int leaf, int block
 // Square-shape checks of da.ExtendShares / rsmt2d for the entry points that keep or export tree nodes (inclusion.cpp)
 int square_k(uint32_t count, uint32_t share_len, uint32_t* k, cda_err_info* err);
 void release_squares(cda_ctx* c);  // sampling.cpp: cda_free's part for the open squares (lock held)
+// repair.cpp: what cda_repair_device runs, for a caller that already holds the lock for `s` (rebuild.cpp): rsmt2d
+// Repair of the square at d_eds (device memory) in place; present (host) is updated
+int repair_resident(cda_ctx* c, uint32_t k, uint8_t* d_eds, uint8_t* present, const uint8_t* row_roots,
+                    const uint8_t* col_roots, cda_err_info* err, hipStream_t s);
 // 96-B records -> packed 90-B nodes
 void pack_roots(const uint8_t* recs, uint32_t n, uint8_t* out);
 // device status word -> CDA_OK / CDA_E_NS_ORDER (+ err detail)

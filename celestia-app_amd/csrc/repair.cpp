@@ -518,6 +518,13 @@ static int repair_impl(cda_ctx* c, uint32_t k, uint8_t* eds, uint8_t* d_eds_in, 
   return finish(solved ? CDA_OK : CDA_E_UNREPAIRABLE, -1, -1);
 }
 
+namespace cda {
+int repair_resident(cda_ctx* c, uint32_t k, uint8_t* d_eds, uint8_t* present, const uint8_t* row_roots,
+                    const uint8_t* col_roots, cda_err_info* err, hipStream_t s) {
+  return repair_impl(c, k, nullptr, d_eds, present, row_roots, col_roots, err, s);
+}
+}  // namespace cda
+
 extern "C" {
 
 int cda_repair(cda_ctx* c, uint32_t k, uint8_t* eds, uint8_t* present, const uint8_t* row_roots,

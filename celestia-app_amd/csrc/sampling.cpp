@@ -22,6 +22,9 @@
 // *_core functions), with the kernels' workspace after its last slot.  Every ensure of a call comes before its first
 // copy: ensure may move a buffer.
 //
+// Building a square is two steps, square_alloc and square_commit (sampling.h), with the EDS put in place between them:
+// by an upload or the extension here, by a device copy or by the assembly and repair of samples in rebuild.cpp.
+//
 // Ownership: a square's device memory is one allocation of its own, so no other call on the context can touch it.
 // The context lists its open squares; cda_free releases their device memory and detaches them (ctx = null), after
 // which a handle is good for cda_square_close alone, which then only frees the host struct.  As for every other
@@ -37,13 +40,6 @@
 #include "sampling.h"
 
 using namespace cda;
-
-struct cda_square {
-  cda_ctx* c = nullptr;  // null once the context was freed
-  uint32_t k = 0;
-  void* mem = nullptr;  // eds | leaf records | level records | data-root tree (SquareView)
-  SquareView view{};
-};
 
 namespace {
 
@@ -69,15 +65,14 @@ void release_squares(cda_ctx* c) {
   c->squares.clear();
 }
 
-}  // namespace cda
+// ---- a square being built (sampling.h): what cda_square_open, cda_square_open_eds and rebuild.cpp's calls share ----
+SquareBuild::~SquareBuild() {
+  if (!sq) return;
+  release_square_memory(sq);
+  delete sq;
+}
 
-namespace {
-
-// What cda_square_open and cda_square_open_eds share: the handle's allocation, the commitment of the EDS in it (leaf
-// hash, levels, DAH and data-root tree), the one copy back and the handle.  extended = false: `src` is the k x k ODS
-// and is extended into the EDS area first; true: `src` is the (2k)^2 EDS and is retained as it is.  Lock held.
-int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_square** out, uint8_t* row_roots,
-                uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
+int square_alloc(cda_ctx* c, uint32_t k, SquareBuild& b, hipStream_t s) {
   const uint32_t w = 2 * k;
   const int L = ilog2i(w);
   const size_t cells = (size_t)w * w, ods_b = (size_t)k * k * CDA_SHARE, eds_b = cells * CDA_SHARE;
@@ -85,34 +80,32 @@ int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_s
   // the ODS is uploaded into the level records' place: the extension has read it before level 1 is written
   // meta: status [0, 8) | dah [256, 288) | data-root tree [512, ..)
   const size_t tail_b = align256(std::max(levels_b, ods_b)), dn = 2 * (size_t)(2 * w) - 1, meta_b = 512 + dn * 32;
-  struct Owner {  // releases a half-built square on every failure path (including an exception)
-    cda_square* sq;
-    ~Owner() {
-      if (!sq) return;
-      release_square_memory(sq);
-      delete sq;
-    }
-  } own{new cda_square()};
-  cda_square* sq = own.sq;
+  b.sq = new cda_square();
   fault_point("alloc");
-  if (!dev_ok(c, hipMalloc(&sq->mem, eds_b + align256(leaf_b) + tail_b + meta_b), "hipMalloc")) return CDA_E_DEVICE;
-  uint8_t* d_eds = (uint8_t*)sq->mem;
-  uint8_t* d_leaf = d_eds + eds_b;
-  uint8_t* d_levels = d_leaf + align256(leaf_b);
-  uint8_t* meta = d_levels + tail_b;
+  if (!dev_ok(c, hipMalloc(&b.sq->mem, eds_b + align256(leaf_b) + tail_b + meta_b), "hipMalloc")) return CDA_E_DEVICE;
+  b.eds = (uint8_t*)b.sq->mem;
+  b.eds_b = eds_b;
+  b.leaf = b.eds + eds_b;
+  b.levels = b.leaf + align256(leaf_b);
+  b.meta = b.levels + tail_b;
+  if (!dev_ok(c, hipMemsetAsync(b.meta, 0xFF, 8, s), "memset")) return CDA_E_DEVICE;
+  return CDA_OK;
+}
+
+int square_commit(cda_ctx* c, uint32_t k, SquareBuild& b, cda_square** out, uint8_t* row_roots, uint8_t* col_roots,
+                  uint8_t* dah, cda_err_info* err, hipStream_t s) {
+  const uint32_t w = 2 * k;
+  const int L = ilog2i(w);
+  cda_square* sq = b.sq;
+  uint8_t* d_eds = b.eds;
+  uint8_t* d_leaf = b.leaf;
+  uint8_t* d_levels = b.levels;
+  uint8_t* meta = b.meta;
   unsigned long long* d_status = (unsigned long long*)meta;
   uint8_t* d_dah = meta + 256;
   uint8_t* d_dnodes = meta + 512;
   auto level = [&](int h) { return d_levels + square_level_offset(L, h) * CDA_REC_BYTES; };
-  hipStream_t s = c->stream;
   int rc;
-  if (!dev_ok(c, hipMemsetAsync(d_status, 0xFF, 8, s), "memset")) return CDA_E_DEVICE;
-  if (extended) {
-    if ((rc = staged_h2d(c, d_eds, src, eds_b, s))) return rc;
-  } else {
-    if (!dev_ok(c, hipMemcpyAsync(d_levels, src, ods_b, hipMemcpyHostToDevice, s), "H2D")) return CDA_E_DEVICE;
-    if ((rc = enqueue_rs(c, k, 1, d_levels, d_eds, s))) return rc;
-  }
   {
     ProfScope ps(c, "leaf_hash", s);
     if (launch_leaf_hash(d_eds, d_leaf, d_status, (int)k, 1, s)) return CDA_E_DEVICE;
@@ -147,9 +140,32 @@ int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_s
   sq->k = k;
   sq->view = SquareView{d_eds, d_leaf, d_levels, L, d_dnodes};
   c->squares.push_back(sq);
-  own.sq = nullptr;
+  b.sq = nullptr;
   *out = sq;
   return CDA_OK;
+}
+
+}  // namespace cda
+
+namespace {
+
+// What cda_square_open and cda_square_open_eds share: the handle's allocation, the EDS into it, its commitment, the
+// one copy back and the handle.  extended = false: `src` is the k x k ODS and is extended into the EDS area first;
+// true: `src` is the (2k)^2 EDS and is retained as it is.  Lock held.
+int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_square** out, uint8_t* row_roots,
+                uint8_t* col_roots, uint8_t* dah, cda_err_info* err) {
+  hipStream_t s = c->stream;
+  SquareBuild b;
+  int rc;
+  if ((rc = square_alloc(c, k, b, s))) return rc;
+  if (extended) {
+    if ((rc = staged_h2d(c, b.eds, src, b.eds_b, s))) return rc;
+  } else {
+    const size_t ods_b = (size_t)k * k * CDA_SHARE;
+    if (!dev_ok(c, hipMemcpyAsync(b.levels, src, ods_b, hipMemcpyHostToDevice, s), "H2D")) return CDA_E_DEVICE;
+    if ((rc = enqueue_rs(c, k, 1, b.levels, b.eds, s))) return rc;
+  }
+  return square_commit(c, k, b, out, row_roots, col_roots, dah, err, s);
 }
 
 // ---- the three verifiers.  Per verifier: the arguments of a call as the caller gave them (host pointers in the host

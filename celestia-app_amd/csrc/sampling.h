@@ -32,6 +32,38 @@ __host__ __device__ inline size_t square_level_offset(int log2w, int h) {
   return 2 * w * (w - (w >> (h - 1)));
 }
 
+}  // namespace cda
+
+struct cda_square {
+  cda_ctx* c = nullptr;  // null once the context was freed
+  uint32_t k = 0;
+  void* mem = nullptr;  // eds | leaf records | level records | data-root tree (SquareView)
+  cda::SquareView view{};
+};
+
+namespace cda {
+
+// A square being built (sampling.cpp): square_alloc makes the handle and its one allocation and sets the order-status
+// word to "no error"; the caller puts the EDS into `eds` on `s` (the k x k ODS may pass through `levels`, which the
+// extension has read before level 1 is written); square_commit commits what lies there (leaf hash, levels, DAH and
+// data-root tree), brings the roots back in its one wait and hands the handle out.  Until then the destructor
+// releases the half-built square, on every failure path (an exception included).  Lock held throughout.
+struct SquareBuild {
+  cda_square* sq = nullptr;
+  uint8_t* eds = nullptr;
+  uint8_t* leaf = nullptr;
+  uint8_t* levels = nullptr;
+  uint8_t* meta = nullptr;  // status [0, 8) | dah [256, 288) | data-root tree [512, ..)
+  size_t eds_b = 0;
+  SquareBuild() = default;
+  SquareBuild(const SquareBuild&) = delete;
+  SquareBuild& operator=(const SquareBuild&) = delete;
+  ~SquareBuild();
+};
+int square_alloc(cda_ctx* c, uint32_t k, SquareBuild& b, hipStream_t s);
+int square_commit(cda_ctx* c, uint32_t k, SquareBuild& b, cda_square** out, uint8_t* row_roots, uint8_t* col_roots,
+                  uint8_t* dah, cda_err_info* err, hipStream_t s);
+
 // cda_nmt_verify's arguments, all device memory (include/cda.h)
 struct VerifyArgs {
   const cda_nmt_proof_desc* descs;
@@ -185,5 +217,34 @@ inline void befp_workspace(BefpArgs& a, Arena& ws) {  // the layout, from a.k an
 int launch_befp_prep(const BefpArgs& a, hipStream_t s);     // B1, B2; descriptors, namespaces, masks
 int launch_befp_gather(const BefpArgs& a, hipStream_t s);   // entry shares -> axis buffers
 int launch_befp_combine(const BefpArgs& a, hipStream_t s);  // the verdicts
+
+// cda_samples_assemble_device's arguments, all device memory (include/cda.h), and its workspace (rebuild.cpp,
+// rebuild_kernels.hip)
+struct AssembleArgs {
+  const cda_sample_desc* descs;
+  const uint8_t* shares;
+  const uint8_t* nodes;
+  const uint8_t* roots;
+  uint8_t* eds;
+  uint8_t* present;
+  uint8_t* statuses;
+  uint32_t k, nsamples, nnodes_total;
+  // workspace.  Per sample: the NMT leg's descriptor, namespace and verdict.  Per cell of the square: the lowest
+  // verified sample that claims it (sample_place_rule.h kSampleNoOwner: none).
+  cda_nmt_proof_desc* nmt_descs;
+  uint8_t* nmt_ns;
+  uint8_t* ok;
+  uint32_t* owner;
+};
+inline void assemble_workspace(AssembleArgs& a, Arena& ws) {  // the layout, from a.k and a.nsamples
+  const size_t n = a.nsamples, cells = 4 * (size_t)a.k * a.k;
+  a.nmt_descs = ws.take<cda_nmt_proof_desc>(n);
+  a.nmt_ns = ws.take<uint8_t>(n * CDA_NAMESPACE_SIZE);
+  a.ok = ws.take<uint8_t>(n);
+  a.owner = ws.take<uint32_t>(cells);
+}
+int launch_sample_prep(const AssembleArgs& a, hipStream_t s);   // malformed check; descriptors, namespaces
+int launch_sample_claim(const AssembleArgs& a, hipStream_t s);  // owner[cell] = the lowest verified sample
+int launch_sample_place(const AssembleArgs& a, hipStream_t s);  // owners' shares -> cells; the statuses
 
 }  // namespace cda

@@ -244,7 +244,7 @@ int cda_nmt_axis_root(cda_ctx* ctx, uint64_t square_size, uint64_t axis_index, u
 int cda_repair(cda_ctx* ctx, uint32_t k, uint8_t* eds, uint8_t* present, const uint8_t* row_roots,
                const uint8_t* col_roots, cda_err_info* err);
 /* The same on a square already in device memory of this ctx's GPU (d_eds, 4k^2*512 bytes, repaired
- * in place; e.g. assembled there by a sampling / reconstruction pipeline, or the output of
+ * in place; e.g. assembled there from proved samples by cda_samples_assemble_device, or the output of
  * cda_extend_commit_device).  present / roots / err are host memory.  Ordered after prior work on
  * `stream` (0 = the null stream); returns when the repair is complete. */
 int cda_repair_device(cda_ctx* ctx, uint32_t k, void* d_eds, uint8_t* present, const uint8_t* row_roots,
@@ -519,6 +519,53 @@ int cda_befp_validate(cda_ctx* ctx, uint32_t k, uint32_t nproofs, const cda_befp
 int cda_befp_validate_device(cda_ctx* ctx, uint32_t k, uint32_t nproofs, const void* d_descs, const void* d_entries,
                              uint32_t nentries, const void* d_shares, const void* d_nodes, uint32_t nnodes_total,
                              const void* d_roots, uint32_t nroots, void* d_verdicts, void* stream);
+
+/* ---- a square rebuilt from proved samples: place, repair, retain ---- */
+/* What a reconstructing full node does between sampling and serving (rsmt2d has no assemble step: it is handed
+ * a square with holes; the rule below is this library's, the Repair and the commitment under it are rsmt2d's
+ * (*ExtendedDataSquare).Repair and da.NewDataAvailabilityHeader as cda_repair and cda_square_open_eds run them).
+ * Sample p: the cell (index, pos) proved in row tree `index` (axis CDA_AXIS_ROW), or the cell (pos, index) proved in
+ * column tree `index` (CDA_AXIS_COL); its share is shares[512 p, 512 p + 512), its proof of leaf [pos, pos + 1) the
+ * nodes[node_off, node_off + nnodes) of 90 B.  The namespace its leaf hashes under is derived: the share's first 29
+ * bytes if index < k and pos < k, else 0xFF x 29. */
+typedef struct {
+  uint32_t axis, index, pos, node_off, nnodes;
+} cda_sample_desc;
+/* statuses[p], one byte per sample.  The lowest-indexed verified sample of a cell is placed, so the result does not
+ * depend on the order of execution. */
+#define CDA_SAMPLE_PLACED 0    /* verified, the lowest-indexed verified sample of its cell: its bytes are the cell */
+#define CDA_SAMPLE_DUPLICATE 1 /* verified, not the lowest, the same bytes as the placed sample */
+#define CDA_SAMPLE_CONFLICT 2  /* verified, not the lowest, other bytes: the cell is committed differently in its row
+                                  tree and its column tree; the placed bytes stay the lowest-indexed sample's */
+#define CDA_SAMPLE_REJECTED 3  /* nmt Proof.VerifyInclusion is false (nodes outside the total included) */
+#define CDA_SAMPLE_MALFORMED 4 /* axis > 1, index >= 2k or pos >= 2k: nothing is read through it */
+/* Verify and place only, every pointer device memory, asynchronous on `stream`: d_eds ((2k)^2 x 512 B) receives the
+ * placed cells and zeros elsewhere, d_present ((2k)^2 bytes) 1 for a placed cell, d_statuses (nsamples bytes) the
+ * CDA_SAMPLE_* of every sample.  d_roots: 4k x 90 B, the row roots then the column roots.  d_shares and d_eds must be
+ * 16-byte aligned, the others 4-byte aligned, else CDA_E_ARG; k a power of two (CDA_E_NOT_POW2), k <= 512
+ * (CDA_E_UNSUPPORTED).  nsamples == 0 is legal: nothing is present.  Uses the context's workspace. */
+int cda_samples_assemble_device(cda_ctx* ctx, uint32_t k, uint32_t nsamples, const void* d_descs, const void* d_shares,
+                                const void* d_nodes, uint32_t nnodes_total, const void* d_roots, void* d_eds,
+                                void* d_present, void* d_statuses, void* stream);
+/* cda_square_open_eds for a square already in this GPU's memory (the output of cda_repair_device or
+ * cda_extend_commit_device; 16-byte aligned): one device-to-device copy into the handle, ordered after prior work on
+ * `stream`, then the same commitment with the same outputs; returns when the handle is complete. */
+int cda_square_open_eds_device(cda_ctx* ctx, uint32_t k, const void* d_eds, cda_square** out, uint8_t* row_roots,
+                               uint8_t* col_roots, uint8_t* dah, cda_err_info* err, void* stream);
+/* The whole chain from host buffers: the samples are staged and assembled straight into a new handle's memory,
+ * repaired there against the given roots (rsmt2d Repair, as cda_repair) and committed in place; the square itself
+ * never crosses the bus unless eds_or_null asks for it.
+ *   CDA_OK              *out is the handle, dah its data root; the handle's roots equal row_roots / col_roots.
+ *   CDA_E_UNREPAIRABLE, CDA_E_BYZANTINE (err->axis / index)
+ *                       *out is NULL; present_or_null and eds_or_null receive the state where rsmt2d stops, as
+ *                       cda_repair returns it.
+ * statuses (nsamples bytes) is written whenever the samples were assembled; present_or_null ((2k)^2 bytes) and
+ * eds_or_null ((2k)^2 x 512 B) are optional.  CDA_E_ARG, CDA_E_NOT_POW2 and CDA_E_UNSUPPORTED (k > 512) come before
+ * any device work. */
+int cda_square_rebuild(cda_ctx* ctx, uint32_t k, uint32_t nsamples, const cda_sample_desc* descs,
+                       const uint8_t* shares, const uint8_t* nodes, uint32_t nnodes_total, const uint8_t* row_roots,
+                       const uint8_t* col_roots, cda_square** out, uint8_t* statuses, uint8_t* present_or_null,
+                       uint8_t* eds_or_null, uint8_t* dah, cda_err_info* err);
 
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
