@@ -61,6 +61,8 @@ EXPORTS = [
     "cda_square_prove_namespace", "cda_nmt_verify_namespace", "cda_nmt_verify_namespace_device",
     "cda_square_open_eds", "cda_befp_validate", "cda_befp_validate_device",
     "cda_samples_assemble_device", "cda_square_open_eds_device", "cda_square_rebuild",
+    "cda_commitment_proof_sizes", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
+    "cda_commitment_proofs_verify_device",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -116,6 +118,26 @@ class ShareProofDesc(ctypes.Structure):
                 ("ns", ctypes.c_uint8 * 29), ("pad_", ctypes.c_uint8 * 3)]
 
 
+class BlobRange(ctypes.Structure):
+    """cda_blob_range: ODS shares [start, start + len), row-major."""
+    _fields_ = [("start", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+class CommitmentRow(ctypes.Structure):
+    """cda_commitment_row: one row of a commitment proof (its subtree roots, its NMTProof nodes, its row proof)."""
+    _fields_ = [("nmt_start", ctypes.c_int32), ("nmt_end", ctypes.c_int32), ("node_off", ctypes.c_uint32),
+                ("nnodes", ctypes.c_uint32), ("root_off", ctypes.c_uint32), ("nroots", ctypes.c_uint32),
+                ("total", ctypes.c_int64), ("index", ctypes.c_int64), ("aunt_off", ctypes.c_uint32),
+                ("naunts", ctypes.c_uint32), ("row", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class CommitmentProofDesc(ctypes.Structure):
+    """cda_commitment_proof_desc: one proof of a cda_commitment_proofs_verify batch."""
+    _fields_ = [("row_off", ctypes.c_uint32), ("nrows", ctypes.c_uint32), ("start_row", ctypes.c_uint32),
+                ("end_row", ctypes.c_uint32), ("data_root", ctypes.c_uint32), ("commitment", ctypes.c_uint32),
+                ("subtree_root_threshold", ctypes.c_uint32), ("ns", ctypes.c_uint8 * 29), ("pad_", ctypes.c_uint8 * 3)]
+
+
 class NamespaceQuery(ctypes.Structure):
     """cda_namespace_query: tree (axis, index).ProveNamespace(ns)."""
     _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("ns", ctypes.c_uint8 * 29),
@@ -167,7 +189,18 @@ NO_LEAF_HASH = 0xFFFFFFFF
 SP_VALID, SP_PROOF_COUNT, SP_DATA_COUNT, SP_NEG_START, SP_EMPTY_RANGE, SP_ROW_COUNT, SP_ROW_PROOFS, SP_ROW_PROOF, \
     SP_SHARE_PROOF, SP_MALFORMED = range(10)
 
+# cda_commitment_proofs_verify's verdicts: 0, or the first of rules C0-C8 that fails (include/cda.h CDA_CP_*)
+CP_VALID, CP_MALFORMED, CP_ROW_COUNT, CP_RANGE, CP_ALIGNMENT, CP_ROOT_COUNT, CP_NAMESPACE, CP_ROW_PROOF, \
+    CP_SUBTREE_ROOTS, CP_COMMITMENT = range(10)
+
 # the same records as numpy rows (whole batches are built as arrays)
+BLOB_RANGE_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4")])
+COMMITMENT_ROW_DTYPE = np.dtype([("nmt_start", "<i4"), ("nmt_end", "<i4"), ("node_off", "<u4"), ("nnodes", "<u4"),
+                                 ("root_off", "<u4"), ("nroots", "<u4"), ("total", "<i8"), ("index", "<i8"),
+                                 ("aunt_off", "<u4"), ("naunts", "<u4"), ("row", "<u4"), ("pad_", "<u4")])
+COMMITMENT_PROOF_DESC_DTYPE = np.dtype([("row_off", "<u4"), ("nrows", "<u4"), ("start_row", "<u4"), ("end_row", "<u4"),
+                                        ("data_root", "<u4"), ("commitment", "<u4"),
+                                        ("subtree_root_threshold", "<u4"), ("ns", "u1", (29,)), ("pad_", "u1", (3,))])
 SHARE_RANGE_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4")])
 SHARE_ROW_DTYPE = np.dtype([("nmt_start", "<i4"), ("nmt_end", "<i4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                             ("total", "<i8"), ("index", "<i8"), ("aunt_off", "<u4"), ("naunts", "<u4"),
@@ -203,8 +236,10 @@ _libs = {}
 _lib_lock = threading.Lock()
 
 
-def lib(path=None):
-    """Load libcda.so, or the build at `path` (raises if it was not built: no silent fallback)."""
+def lib(path=None, older=False):
+    """Load libcda.so, or the build at `path` (raises if it was not built: no silent fallback).  older: `path` is a
+    build of an earlier commit (an A/B probe's other side): the calls it lacks are left unbound instead of refused;
+    a Context(lib_path=path) made afterwards uses it."""
     path = path or LIB_PATH
     with _lib_lock:
         if path not in _libs:
@@ -279,8 +314,16 @@ def lib(path=None):
                 "cda_samples_assemble_device": (I32, [P, U32, U32, P, P, P, U32, P, P, P, P, P]),
                 "cda_square_open_eds_device": (I32, [P, U32, P, ctypes.POINTER(P), P, P, P, P, P]),
                 "cda_square_rebuild": (I32, [P, U32, U32, P, P, P, U32, P, P, ctypes.POINTER(P), P, P, P, P, P]),
+                "cda_commitment_proof_sizes": (I32, [U32, U32, U32, P, P, P]),
+                "cda_square_commitment_proofs": (I32, [P, U32, P, U32, U32, U32, U32, P, P, P, P, P, P, P, P, P]),
+                "cda_commitment_proofs_verify": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32, P, U32,
+                                                         P]),
+                "cda_commitment_proofs_verify_device": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32,
+                                                                P, U32, P, P]),
             }
             for name, (res, args) in sig.items():
+                if older and not hasattr(L, name):
+                    continue
                 f = getattr(L, name)
                 f.restype = res
                 f.argtypes = args
@@ -676,6 +719,44 @@ class Context:
                                                       V(stream or 0))
         _check(rc, ctx=self)
 
+    def commitment_proofs_verify(self, descs, rows, row_roots, leaf_hashes, nodes, subtree_roots, aunts, data_roots,
+                                 commitments):
+        """cda_commitment_proofs_verify: rules C0-C8 of a batch.  descs: COMMITMENT_PROOF_DESC_DTYPE rows; rows:
+        COMMITMENT_ROW_DTYPE rows with row_roots (nrows, 90) and leaf_hashes (nrows, 32); nodes and subtree_roots
+        (n, 90); aunts, data_roots and commitments (n, 32), all uint8.  -> verdicts (nproofs,) int32, CP_* codes."""
+        descs = np.ascontiguousarray(descs, COMMITMENT_PROOF_DESC_DTYPE)
+        rows = np.ascontiguousarray(rows, COMMITMENT_ROW_DTYPE)
+        nrows = len(rows)
+        row_roots = np.ascontiguousarray(row_roots, np.uint8).reshape(nrows, NODE_SIZE)
+        leaf_hashes = np.ascontiguousarray(leaf_hashes, np.uint8).reshape(nrows, 32)
+        nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, NODE_SIZE)
+        subtree_roots = np.ascontiguousarray(subtree_roots, np.uint8).reshape(-1, NODE_SIZE)
+        aunts = np.ascontiguousarray(aunts, np.uint8).reshape(-1, 32)
+        data_roots = np.ascontiguousarray(data_roots, np.uint8).reshape(-1, 32)
+        commitments = np.ascontiguousarray(commitments, np.uint8).reshape(-1, 32)
+        verdicts = np.full(len(descs), -1, np.int32)
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_commitment_proofs_verify(self._h, len(descs), p(descs), p(rows), p(row_roots), p(leaf_hashes),
+                                                  nrows, p(nodes), len(nodes), p(subtree_roots), len(subtree_roots),
+                                                  p(aunts), len(aunts), p(data_roots), len(data_roots), p(commitments),
+                                                  len(commitments), _p(verdicts))
+        _check(rc, ctx=self)
+        return verdicts
+
+    def commitment_proofs_verify_device(self, nproofs, d_descs, d_rows, d_row_roots, d_leaf_hashes, nrows, d_nodes,
+                                        nnodes, d_subtree_roots, nsubtree_roots, d_aunts, naunts, d_data_roots, nroots,
+                                        d_commitments, ncommitments, d_verdicts, stream=None):
+        """cda_commitment_proofs_verify_device: the same with device addresses, asynchronous on `stream`."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_commitment_proofs_verify_device(self._h, nproofs, V(d_descs), V(d_rows), V(d_row_roots),
+                                                         V(d_leaf_hashes), nrows, V(d_nodes), nnodes,
+                                                         V(d_subtree_roots), nsubtree_roots, V(d_aunts), naunts,
+                                                         V(d_data_roots), nroots, V(d_commitments), ncommitments,
+                                                         V(d_verdicts), V(stream or 0))
+        _check(rc, ctx=self)
+
     def nmt_verify_namespace(self, descs, namespaces, roots, nodes, leaf_hashes, leaves):
         """cda_nmt_verify_namespace: nmt Proof.VerifyNamespace of a batch.  descs: NMT_NS_PROOF_DESC_DTYPE rows;
         namespaces (nproofs, 29); roots (nroots, 90); nodes (nnodes, 90); leaf_hashes (n, 90); leaves (nleaves, 512), all
@@ -936,6 +1017,72 @@ class Square:
                                     for r in range(lo, hi)], int(rows[lo]["row"]), int(rows[hi - 1]["row"]))
             out.append(P.ShareProof(data, nmt, ns[1:], row_proof, ns[0], raw["data_root"]))
         return out
+
+    @staticmethod
+    def blob_ranges(ranges):
+        """(start, len) tuples -> BLOB_RANGE_DTYPE rows."""
+        return np.array([(int(s), int(n)) for s, n in ranges], BLOB_RANGE_DTYPE).reshape(-1)
+
+    def commitment_proof_sizes(self, ranges, threshold=64):
+        """cda_commitment_proof_sizes: (row records, subtree roots) the commitment proofs of `ranges` ((start, len) ODS
+        share ranges) take under `threshold`; CdaError(E_ARG) for a range the prover rejects."""
+        q = self.blob_ranges(ranges)
+        nrows, nroots = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._ctx._L.cda_commitment_proof_sizes(self.k, threshold, len(q), _p(q), ctypes.byref(nrows),
+                                                       ctypes.byref(nroots)))
+        return nrows.value, nroots.value
+
+    def commitments(self, ranges, threshold=64):
+        """GetCommitment (pkg/inclusion/get_commit.go) of every (start, len) blob of the retained square in one call:
+        cda_square_commitment_proofs with the commitments alone -> list of 32-byte commitments."""
+        q = self.blob_ranges(ranges)
+        out = np.zeros((len(q), 32), np.uint8)
+        rc = self._ctx._L.cda_square_commitment_proofs(self._h, len(q), _p(q), threshold, 0, 0, 0, None, None, None, None,
+                                                       None, None, None, _p(out), None)
+        _check(rc, ctx=self._ctx)
+        return [x.tobytes() for x in out]
+
+    def commitment_proofs_raw(self, ranges, threshold=64, rows_cap=None, roots_cap=None):
+        """cda_square_commitment_proofs -> dict of the flat arrays the call writes: row_off (nq + 1,), rows
+        (COMMITMENT_ROW_DTYPE), nodes (nrows, max_nodes, 90), subtree_roots (nroots, 90), row_roots (nrows, 90),
+        leaf_hashes (nrows, 32), aunts (nrows, log2(4k), 32), commitments (nq, 32), data_root bytes.  Blob q's records
+        are rows[row_off[q]:row_off[q + 1]].  rows_cap / roots_cap: the capacities handed to the call (default: what
+        cda_commitment_proof_sizes says)."""
+        q = self.blob_ranges(ranges)
+        nq, mn, na = len(q), max(1, self.max_nodes), (4 * self.k).bit_length() - 1
+        nrows, nroots = self.commitment_proof_sizes(ranges, threshold)
+        nrows = nrows if rows_cap is None else rows_cap
+        nroots = nroots if roots_cap is None else roots_cap
+        out = {"row_off": np.zeros(nq + 1, np.uint32), "rows": np.zeros(nrows, COMMITMENT_ROW_DTYPE),
+               "nodes": np.zeros((nrows, mn, NODE_SIZE), np.uint8), "subtree_roots": np.zeros((nroots, NODE_SIZE), np.uint8),
+               "row_roots": np.zeros((nrows, NODE_SIZE), np.uint8), "leaf_hashes": np.zeros((nrows, 32), np.uint8),
+               "aunts": np.zeros((nrows, na, 32), np.uint8), "commitments": np.zeros((nq, 32), np.uint8)}
+        root = np.zeros(32, np.uint8)
+        rc = self._ctx._L.cda_square_commitment_proofs(self._h, nq, _p(q), threshold, mn, nrows, nroots,
+                                                       _p(out["row_off"]), _p(out["rows"]), _p(out["nodes"]),
+                                                       _p(out["subtree_roots"]), _p(out["row_roots"]),
+                                                       _p(out["leaf_hashes"]), _p(out["aunts"]), _p(out["commitments"]),
+                                                       _p(root))
+        _check(rc, ctx=self._ctx)
+        out["data_root"] = root.tobytes()
+        return out
+
+    def commitment_proofs_device(self, ranges, threshold, max_nodes, rows_cap, roots_cap, d_row_off, d_rows, d_nodes,
+                                 d_subtree_roots, d_row_roots, d_leaf_hashes, d_aunts, d_commitments, d_data_root):
+        """cda_square_commitment_proofs with the outputs at device addresses (the ranges stay host records)."""
+        q = self.blob_ranges(ranges)
+        V = ctypes.c_void_p
+        rc = self._ctx._L.cda_square_commitment_proofs(self._h, len(q), _p(q), threshold, max_nodes, rows_cap, roots_cap,
+                                                       V(d_row_off), V(d_rows), V(d_nodes), V(d_subtree_roots),
+                                                       V(d_row_roots), V(d_leaf_hashes), V(d_aunts), V(d_commitments),
+                                                       V(d_data_root))
+        _check(rc, ctx=self._ctx)
+
+    def commitment_proofs(self, ranges, namespaces, threshold=64):
+        """ADR-011's blob inclusion proof for every (start, len) blob of the retained square, one call -> list of
+        cda.commitment.CommitmentProof; namespaces: the 29-byte namespace of each blob."""
+        from . import commitment as C
+        return C.proofs_from_raw(self.commitment_proofs_raw(ranges, threshold), namespaces)
 
     @staticmethod
     def namespace_queries(queries):

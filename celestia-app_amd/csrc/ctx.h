@@ -137,6 +137,10 @@ size_t staged_bytes(Lay& lay) {
   lay(measure);
   return measure.ar.used();
 }
+// copy to or from caller memory that may be host or device memory (the provers' outputs)
+inline bool copy_any(cda_ctx* c, void* dst, const void* src, size_t n, hipStream_t s) {
+  return n == 0 || dev_ok(c, hipMemcpyAsync(dst, src, n, hipMemcpyDefault, s), "copy");
+}
 // the end of a host-form verifier: the verdicts back, the call's one wait, the profile
 inline int verdicts_back(cda_ctx* c, void* dst, const void* d_src, size_t n, hipStream_t s) {
   if (!dev_ok(c, hipMemcpyAsync(dst, d_src, n, hipMemcpyDeviceToHost, s), "D2H") ||

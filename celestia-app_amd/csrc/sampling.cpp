@@ -48,11 +48,6 @@ void release_square_memory(cda_square* sq) {
   sq->mem = nullptr;
 }
 
-// copy to or from caller memory that may be host or device memory
-bool copy_any(cda_ctx* c, void* dst, const void* src, size_t n, hipStream_t s) {
-  return n == 0 || dev_ok(c, hipMemcpyAsync(dst, src, n, hipMemcpyDefault, s), "copy");
-}
-
 }  // namespace
 
 namespace cda {

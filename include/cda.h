@@ -427,6 +427,93 @@ int cda_share_proofs_validate_device(cda_ctx* ctx, uint32_t nproofs, const void*
                                      const void* d_leaves, uint32_t nleaves, const void* d_data_roots,
                                      uint32_t nroots, void* d_verdicts, void* stream);
 
+/* ---- blob commitment proofs: "the blob with share commitment C is in the block with data root R", without the
+ * blob's shares (ADR-011 "Blob Inclusion Proof"): the blob's subtree roots, their proofs to the row roots and on to
+ * the data root, and the commitment over the subtree roots.  Parity unpinned: the verifier's rule list C0-C8 is this
+ * project's statement; its counterpart lives in celestia-node and nmt, outside the reference tree. ---- */
+/* ODS shares [start, start + len), row-major: a blob as square.Construct placed it (start a multiple of its
+ * SubTreeWidth). */
+typedef struct {
+  uint32_t start, len;
+} cda_blob_range;
+/* One row of a commitment proof.  Row record r goes with row_roots[r] (90 B) and leaf_hashes[r] (32 B), as a
+ * cda_share_row does. */
+typedef struct {
+  int32_t nmt_start, nmt_end; /* the row's leaf range, as cda_share_row */
+  uint32_t node_off, nnodes;  /* ProveRange(nmt_start, nmt_end) of the row tree = nodes[node_off, +nnodes) of 90 B */
+  uint32_t root_off, nroots;  /* the range's subtree roots = subtree_roots[root_off, +nroots) of 90 B, left to right */
+  int64_t total, index;       /* Proof.Total / Index of the row root in the data root: 4k, row */
+  uint32_t aunt_off, naunts;  /* Proof.Aunts = aunts[aunt_off, +naunts) of 32 B, bottom-up */
+  uint32_t row;               /* the row of the square (the prover's; the verifier ignores it) */
+  uint32_t pad_;
+} cda_commitment_row;
+/* The row records and subtree roots cda_square_commitment_proofs writes for nq ranges of a k x k square under
+ * subtree_root_threshold.  CDA_E_ARG for what that call rejects in a range (below), CDA_E_NOT_POW2 for k. */
+int cda_commitment_proof_sizes(uint32_t k, uint32_t subtree_root_threshold, uint32_t nq, const cda_blob_range* q,
+                               uint64_t* nrows, uint64_t* nroots);
+/* Commitment proofs of nq blobs of a retained square in one call: nothing is extended or hashed again but the
+ * commitments.  Blob q has W = SubTreeWidth(len, subtree_root_threshold) and rows start / k .. (start + len - 1) / k;
+ * its row records are rows[row_off[q], row_off[q + 1]) (row_off: nq + 1 words) and its subtree roots lie contiguous in
+ * subtree_roots, row after row, left to right (pkg/inclusion/paths.go's coordinates).  Record r has node_off =
+ * r * max_nodes (the slots after its nnodes nodes are zero), aunt_off = r * log2(4k), naunts = log2(4k), total = 4k,
+ * index = row.  commitments[q] (32 B) = merkle.HashFromByteSlices over blob q's subtree roots = GetCommitment
+ * (pkg/inclusion/get_commit.go).  Capacities: rows_cap row records in rows / nodes (x max_nodes x 90 B) / row_roots
+ * (x 90) / leaf_hashes (x 32) / aunts (x log2(4k) x 32); roots_cap subtree roots of 90 B.  data_root: 32 B, once.
+ * Commitments only: row_off, rows, nodes, subtree_roots, row_roots, leaf_hashes, aunts and data_root all NULL (the
+ * capacities are then ignored).  CDA_E_ARG before any launch for len == 0, a range outside the ODS, threshold == 0,
+ * W > k, start % W != 0, max_nodes < 2 log2(2k) or a capacity too small; CDA_E_UNSUPPORTED for a blob of more than
+ * 262,144 subtree roots.  q is host memory; every output may be host or device memory. */
+int cda_square_commitment_proofs(cda_square* sq, uint32_t nq, const cda_blob_range* q,
+                                 uint32_t subtree_root_threshold, uint32_t max_nodes, uint32_t rows_cap,
+                                 uint32_t roots_cap, uint32_t* row_off, cda_commitment_row* rows, uint8_t* nodes,
+                                 uint8_t* subtree_roots, uint8_t* row_roots, uint8_t* leaf_hashes, uint8_t* aunts,
+                                 uint8_t* commitments, uint8_t* data_root);
+
+/* One commitment proof of a cda_commitment_proofs_verify batch over flat arrays: its rows are the row records
+ * [row_off, row_off + nrows); it is verified against data_roots[data_root] and commitments[commitment]. */
+typedef struct {
+  uint32_t row_off, nrows;
+  uint32_t start_row, end_row;
+  uint32_t data_root, commitment;
+  uint32_t subtree_root_threshold;
+  uint8_t ns[29]; /* the blob's namespace: NamespaceVersion ‖ NamespaceID */
+  uint8_t pad_[3];
+} cda_commitment_proof_desc;
+/* Verdicts: 0, or the first rule that fails, in this order. */
+enum {
+  CDA_CP_VALID = 0,
+  CDA_CP_MALFORMED = 1,     /* C0: offsets or counts outside the totals, nrows == 0, threshold == 0, more than 262,144
+                               subtree roots, or row records shared with another proof: nothing is read through it */
+  CDA_CP_ROW_COUNT = 2,     /* C1: end_row - start_row + 1 != nrows */
+  CDA_CP_RANGE = 3,         /* C2: the rows' ranges are not one contiguous range of a k x k ODS (total = 4k, index =
+                               start_row + i, 0 <= nmt_start < nmt_end <= k, inner edges at 0 and k) */
+  CDA_CP_ALIGNMENT = 4,     /* C3: W = SubTreeWidth(sum of the ranges, threshold) > k, or the first nmt_start % W != 0 */
+  CDA_CP_ROOT_COUNT = 5,    /* C4: a row's nroots is not the number of tiles of its range under W */
+  CDA_CP_NAMESPACE = 6,     /* C5: a subtree root whose min or max namespace is not ns */
+  CDA_CP_ROW_PROOF = 7,     /* C6: merkle Proof.Verify of a row root in the data root fails */
+  CDA_CP_SUBTREE_ROOTS = 8, /* C7: a row's subtree roots and nodes do not fold to its row root (wrong node count or
+                               sibling order included) */
+  CDA_CP_COMMITMENT = 9,    /* C8: the RFC-6962 root over all subtree roots, in order, is not the commitment */
+};
+/* Batched verification: verdicts[p] (int32) for proof p.  A false proof is a verdict, never an error code.  The arrays
+ * cda_square_commitment_proofs writes are accepted as they lie.  nrows / nnodes / nsubtree_roots / naunts / nroots /
+ * ncommitments are the totals of rows (and row_roots, leaf_hashes) / nodes / subtree_roots / aunts / data_roots /
+ * commitments. */
+int cda_commitment_proofs_verify(cda_ctx* ctx, uint32_t nproofs, const cda_commitment_proof_desc* descs,
+                                 const cda_commitment_row* rows, const uint8_t* row_roots, const uint8_t* leaf_hashes,
+                                 uint32_t nrows, const uint8_t* nodes, uint32_t nnodes, const uint8_t* subtree_roots,
+                                 uint32_t nsubtree_roots, const uint8_t* aunts, uint32_t naunts,
+                                 const uint8_t* data_roots, uint32_t nroots, const uint8_t* commitments,
+                                 uint32_t ncommitments, int32_t* verdicts);
+/* The same with every pointer in device memory (d_rows 8-byte, the others 4-byte aligned, else CDA_E_ARG),
+ * asynchronous on `stream`; every check is made in the kernels.  Uses the context's workspace. */
+int cda_commitment_proofs_verify_device(cda_ctx* ctx, uint32_t nproofs, const void* d_descs, const void* d_rows,
+                                        const void* d_row_roots, const void* d_leaf_hashes, uint32_t nrows,
+                                        const void* d_nodes, uint32_t nnodes, const void* d_subtree_roots,
+                                        uint32_t nsubtree_roots, const void* d_aunts, uint32_t naunts,
+                                        const void* d_data_roots, uint32_t nroots, const void* d_commitments,
+                                        uint32_t ncommitments, void* d_verdicts, void* stream);
+
 /* ---- namespace data with completeness proofs: nmt ProveNamespace / Proof.VerifyNamespace, batched ---- */
 /* "Everything of namespace ns in tree (axis, index), and a proof that nothing was withheld."  Namespaces compare as
  * 29-byte big-endian strings; leaf i's namespace is the share's own in Q0 and 0xFF x 29 elsewhere. */
