@@ -64,6 +64,13 @@ int rs_decode_init_device_tables(int device);
 int launch_rs_decode(uint8_t* d_base, const long long* d_off, const long long* d_stride, const uint8_t* d_present,
                      int ncw, int k, int shard_len, hipStream_t s);
 int launch_rs_encode8(const RsJob& job, hipStream_t s);
+// launch_rs_encode8 takes the two-codeword register encoder for the whole of this job (not the LDS or latency form)
+bool rs8_reg_batched(const RsJob& job);
+// two such jobs of the same shape (512-B shards) in one launch, block-major: block b's workgroups of ja, then its
+// workgroups of jb (neither with a cpy target); remap: XCD-contiguous workgroup order.  -2: not that shape
+int launch_rs_encode8_pair(const RsJob& ja, const RsJob& jb, bool remap, hipStream_t s);
+// Q0 of nblocks EDS blocks from the contiguous ODS blocks (k a power of two); max_wgs > 0 caps the grid
+int launch_q0_copy(const uint8_t* d_ods, uint8_t* d_eds, int k, int nblocks, int max_wgs, hipStream_t s);
 int launch_rs_encode16(const RsJob& job, hipStream_t s);
 // register-resident GF(2^16) encoder for k = 512 (rs16_kernels.hip)
 bool rs16_reg_eligible(const RsJob& j);
@@ -72,8 +79,9 @@ const char* rs16_diag_tag();
 const char* rs8_diag_tag();
 int rs16_reg_init(int device);
 int launch_rs_encode16_reg(const RsJob& j, const uint16_t* d_cpoly, hipStream_t s);
+// d_ods (optional): the contiguous ODS blocks; Q0 cells are then read from there and Q0 of d_eds is not read
 int launch_leaf_hash(const uint8_t* d_eds, void* d_leaf_nodes, unsigned long long* d_status, int k, int nblocks,
-                     hipStream_t s);
+                     hipStream_t s, const uint8_t* d_ods = nullptr);
 int launch_nmt_level(const void* d_in, void* d_out, bool from_leaves, int k, int nblocks, int level, hipStream_t s);
 // Leaf records -> all 4k roots of nblocks blocks, several levels per launch; d_levels: nblocks x 2w x w
 // records of scratch for the inner levels.  prof_ctx: the cda_ctx for ProfScope (or null).  l1_quads: level 1 from

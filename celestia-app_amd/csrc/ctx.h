@@ -35,6 +35,27 @@ struct cda_ctx {
   bool repair_early = true;
   // CDA_L1_QUADS=0: tree levels 1-2 in one nmt_levels_kernel launch instead of the quad kernel + a level-2 launch
   bool l1_quads = true;
+  // RS schedule of a batch that takes the register encoder (enqueue_pipeline).  2: Q1 and Q2 straight
+  // from the ODS in one launch, Q3 from Q2, the Q0 copy on q0_stream beside the hashing, which reads Q0 cells from
+  // the ODS.  CDA_RS_SCHED=1: the same launches with the copy on the caller's stream before the leaf kernel;
+  // CDA_RS_SCHED=0: the two passes (rows with the Q0 copy, then columns of the top half).
+  int rs_sched = 2;
+  // smallest ODS of a call (bytes, all blocks) that takes schedule 1 or 2; CDA_RS_MIN_ODS_MIB (engine.cpp rs_from_ods)
+  size_t rs_min_ods_bytes = (size_t)256 << 20;
+  // CDA_RS_Q3=cols: Q3 from Q1 by columns instead of from Q2 by rows (the same code word)
+  bool rs_q3_cols = false;
+  // CDA_RS_PAIR_REMAP=1: the Q1 + Q2 launch in XCD-contiguous workgroup order instead of plain order
+  bool rs_pair_remap = false;
+  // CDA_Q0_COPY_WGS: workgroups of the Q0 copy on q0_stream, each walking 16 KiB chunks (0: one per chunk).  Tuned
+  // at one shape only, k = 128 and B = 128 on the default stream, where the window is narrow: 96-128 cost the leaf
+  // kernel more, 32 makes the copy outlast the hashing (-18 %).  Copy and hashing both scale with the cell count,
+  // but no other k or B and no concurrent H2D / D2H traffic was measured.
+  int q0_copy_wgs = 64;
+  // the Q0 copy's stream and its fork / join events with the caller's stream.  A fifth stream: by the round-robin
+  // below it shares c->stream's hardware queue, so it is used only beside a caller's own stream (engine.cpp
+  // rs_from_ods); calls that run on c->stream keep the two passes.
+  hipStream_t q0_stream = nullptr;
+  hipEvent_t q0_fork_ev = nullptr, q0_join_ev = nullptr;
   // HIP maps streams round-robin onto GPU_MAX_HW_QUEUES (4) hardware queues, so the streams that must run
   // concurrently are created first, together: stream, h2d_stream, d2h_stream, aux_stream.
   hipStream_t aux_stream = nullptr;

@@ -10,6 +10,8 @@
 //   4. nmt_levels           : row and column trees of every block: level 1 by 2x2 cell quads, level 2, then 2 (or 3)
 //                             levels per launch
 //   5. dah                  : RFC-6962 over row roots ‖ col roots
+// A batch on the register encoder replaces 1-2 (enqueue_rs_from_ods): Q1 and Q2 straight from the ODS in one launch,
+// Q3 from Q2 by rows, and the Q0 copy on a second stream beside 3-5, where the leaf kernel reads Q0 cells from the ODS.
 // rsmt2d Repair lives in repair.cpp, the host-buffer batch pipeline in host_pipeline.cpp.
 // Nothing here computes on the CPU: the host only validates arguments, moves
 // buffers and maps device status words to error codes.
@@ -207,6 +209,68 @@ int enqueue_rs(cda_ctx* c, uint32_t k, uint32_t nblocks, const uint8_t* d_ods, u
   return CDA_OK;
 }
 
+// The batched block path's other RS schedule: Q1 by rows and Q2 by columns, both straight from the
+// ODS, in one launch; then Q3 from Q2 by rows (or from Q1 by columns: the product code commutes).  Neither launch
+// writes Q0: the caller copies it (enqueue_pipeline).  For whole batches on the two-codeword register encoder only;
+// an ODS inside the EDS buffer keeps the two passes.
+static RsJob quadrant_job(uint32_t k, uint32_t nblocks, const uint8_t* src, long long src_blk, long long src_pitch,
+                          uint8_t* dst, bool by_cols) {
+  const uint32_t w = 2 * k;
+  const long long S = CDA_SHARE;
+  RsJob j{};
+  j.src = src;
+  j.src_blk = src_blk;
+  j.src_cw = by_cols ? S : src_pitch;
+  j.src_sh = by_cols ? src_pitch : S;
+  j.dst = dst;
+  j.dst_blk = (long long)w * w * S;
+  j.dst_cw = by_cols ? S : (long long)w * S;
+  j.dst_sh = by_cols ? (long long)w * S : S;
+  j.k = (int)k;
+  j.cw_per_blk = (int)k;
+  j.nblk = (int)nblocks;
+  j.shard_len = CDA_SHARE;
+  return j;
+}
+
+static bool rs_from_ods(const cda_ctx* c, uint32_t k, uint32_t nblocks, const uint8_t* d_ods, const uint8_t* d_eds,
+                        hipStream_t s) {
+  // Only batches on a caller's stream.  Work on c->stream (the host-buffer batch, square construction, the
+  // synchronous calls) keeps the two passes: q0_stream is the context's fifth stream and by HIP's round-robin shares
+  // c->stream's hardware queue, where the copy serialises with the hashing (host batch of 24 blocks, roots only: 4.95
+  // against 4.29 ms; on a queue of its own it equals the two passes, the path being bound by PCIe).  Small batches
+  // keep them too: the fork and join cost 6-9 us a call (k = 128: B = 1, 2, 8 came out 9, 6 and 9 us slower), the
+  // schedule saves 0.9 us per k = 128 block, so it breaks even near 80 MiB of ODS; taken from 256 MiB on.
+  const uintptr_t ods_bytes = (uintptr_t)nblocks * k * k * CDA_SHARE;
+  if (c->rs_sched == 0 || s == c->stream || ods_bytes < c->rs_min_ods_bytes) return false;
+  // k a power of two: the copy kernel's precondition, so that the choice is made before anything is launched
+  if (2 * k > 256 || !is_pow2(k) || !rs8_reg_batched(rows_job(k, nblocks, d_ods, const_cast<uint8_t*>(d_eds))))
+    return false;
+  const uintptr_t o = (uintptr_t)d_ods, e = (uintptr_t)d_eds, ods_b = (uintptr_t)nblocks * k * k * CDA_SHARE;
+  return o + ods_b <= e || e + 4 * ods_b <= o;
+}
+
+static int enqueue_rs_from_ods(cda_ctx* c, uint32_t k, uint32_t nblocks, const uint8_t* d_ods, uint8_t* d_eds,
+                               hipStream_t s) {
+  const long long S = CDA_SHARE, w = 2 * k, eds_blk = w * w * S;
+  uint8_t *q1 = d_eds + k * S, *q2 = d_eds + k * w * S, *q3 = q2 + k * S;
+  {
+    const RsJob ja = quadrant_job(k, nblocks, d_ods, (long long)k * k * S, k * S, q1, false);
+    const RsJob jb = quadrant_job(k, nblocks, d_ods, (long long)k * k * S, k * S, q2, true);
+    ProfScope ps(c, "rs_encode8_rows", s);
+    const int lr = launch_rs_encode8_pair(ja, jb, c->rs_pair_remap, s);
+    if (lr) return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;
+  }
+  {
+    const RsJob j = c->rs_q3_cols ? quadrant_job(k, nblocks, q1, eds_blk, w * S, q3, true)
+                                  : quadrant_job(k, nblocks, q2, eds_blk, w * S, q3, false);
+    ProfScope ps(c, "rs_encode8_cols", s);
+    const int lr = launch_rs_encode8(j, s);
+    if (lr) return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;
+  }
+  return CDA_OK;
+}
+
 // Commitment phase: leaf hashing, NMT levels, DAH of nblocks extended blocks.
 // NMT levels + DAH of nblocks blocks whose leaf records are at record offset rec_off.
 // small batches (latency: the consensus path extends one block): all trees + the DAH in one LDS-resident launch
@@ -285,8 +349,38 @@ int enqueue_pipeline(cda_ctx* c, uint32_t k, uint32_t nblocks, const uint8_t* d_
   // the order-status words are set before the extension, so no fill sits between the column pass and the leaf
   // hashing on the dependent chain of a one-block call
   if (!dev_ok(c, hipMemsetAsync(d_status, 0xFF, (size_t)nblocks * 8, s), "hipMemsetAsync")) return CDA_E_DEVICE;
-  if ((rc = enqueue_rs(c, k, nblocks, d_ods, d_eds, s))) return rc;
-  return enqueue_commit(c, k, nblocks, d_eds, d_roots, d_dah, d_status, s, 0, false);
+  if (!rs_from_ods(c, k, nblocks, d_ods, d_eds, s)) {
+    if ((rc = enqueue_rs(c, k, nblocks, d_ods, d_eds, s))) return rc;
+    return enqueue_commit(c, k, nblocks, d_eds, d_roots, d_dah, d_status, s, 0, false);
+  }
+  if ((rc = enqueue_rs_from_ods(c, k, nblocks, d_ods, d_eds, s))) return rc;
+  const bool side = c->rs_sched == 2;
+  const hipStream_t q0s = c->q0_stream;
+  // the copy starts once the HBM-bound launches are through and runs beside the hashing, on few workgroups: the
+  // hash kernels leave most of HBM idle but slow down behind a copy that takes all of it
+  if (side && (!dev_ok(c, hipEventRecord(c->q0_fork_ev, s), "hipEventRecord") ||
+               !dev_ok(c, hipStreamWaitEvent(q0s, c->q0_fork_ev, 0), "hipStreamWaitEvent")))
+    return CDA_E_DEVICE;
+  if (const int lr = launch_q0_copy(d_ods, d_eds, (int)k, (int)nblocks, side ? c->q0_copy_wgs : 0,
+                                    side ? q0s : s))
+    return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE;  // nothing was put on q0_stream
+  if (side && !dev_ok(c, hipEventRecord(c->q0_join_ev, q0s), "hipEventRecord")) {
+    (void)hipStreamSynchronize(q0s);  // no event to join on: the copy is waited for here
+    return CDA_E_DEVICE;
+  }
+  {
+    ProfScope ps(c, "leaf_hash", s);
+    if (launch_leaf_hash(d_eds, bufs0(c, 0), d_status, (int)k, (int)nblocks, s, side ? d_ods : nullptr))
+      rc = CDA_E_DEVICE;
+  }
+  if (!rc) rc = enqueue_trees(c, k, nblocks, d_roots, d_dah, s, 0);
+  // the join comes last, also when a launch behind the copy failed: whatever the caller orders after this call
+  // sees the whole EDS, and the next call's copy is ordered after this one's
+  if (side && !dev_ok(c, hipStreamWaitEvent(s, c->q0_join_ev, 0), "hipStreamWaitEvent")) {
+    (void)hipStreamSynchronize(q0s);
+    return CDA_E_DEVICE;
+  }
+  return rc;
 }
 
 // 96-B records -> packed 90-B nodes
@@ -343,11 +437,20 @@ int cda_init(int device, cda_ctx** out) {
   if (const char* e = getenv("CDA_COPY_THREADS")) c->copy_threads = std::max(1, std::min(64, atoi(e)));
   if (const char* e = CDA_AB_ENV("CDA_HUGE_PAGES")) c->huge_pages = atoi(e) != 0;
   c->cons_trace = CDA_AB_ENV("CDA_CONS_TRACE") != nullptr;
+  // the block path's RS schedule (ctx.h)
+  if (const char* e = CDA_AB_ENV("CDA_RS_SCHED")) c->rs_sched = std::max(0, std::min(2, atoi(e)));
+  if (const char* e = CDA_AB_ENV("CDA_RS_MIN_ODS_MIB")) c->rs_min_ods_bytes = (size_t)std::max(0, atoi(e)) << 20;
+  if (const char* e = CDA_AB_ENV("CDA_RS_Q3")) c->rs_q3_cols = e[0] == 'c';
+  if (const char* e = CDA_AB_ENV("CDA_RS_PAIR_REMAP")) c->rs_pair_remap = atoi(e) != 0;
+  if (const char* e = CDA_AB_ENV("CDA_Q0_COPY_WGS")) c->q0_copy_wgs = std::max(0, atoi(e));
   find_local_cpus(c);
   // the streams that overlap each other, created right after `stream` so that they land on distinct hardware
   // queues (HIP assigns streams to its GPU_MAX_HW_QUEUES = 4 queues round-robin)
   bool ok = ensure_pipeline(c) == CDA_OK &&
             hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) == hipSuccess &&
+            hipStreamCreateWithFlags(&c->q0_stream, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&c->q0_fork_ev, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&c->q0_join_ev, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&c->sync_ev, hipEventDisableTiming) == hipSuccess;
@@ -382,6 +485,9 @@ void cda_free(cda_ctx* c) {
     free_pipeline(c);
     free_staging(c);
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
+    if (c->q0_stream) (void)hipStreamDestroy(c->q0_stream);
+    if (c->q0_fork_ev) (void)hipEventDestroy(c->q0_fork_ev);
+    if (c->q0_join_ev) (void)hipEventDestroy(c->q0_join_ev);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->ws_event) (void)hipEventDestroy(c->ws_event);
     if (c->sync_ev) (void)hipEventDestroy(c->sync_ev);

@@ -274,7 +274,7 @@ int cda_host_unregister(cda_ctx* c, void* p) {
   // synchronous entry points return only after their copies completed, and the copy streams (h2d / d2h: the batch
   // pipeline, the one-block path, repair; aux: repair's verification) and the main stream are drained here as well,
   // so this holds whatever a future entry point leaves in flight.
-  for (hipStream_t s : {c->stream, c->h2d_stream, c->d2h_stream, c->aux_stream})
+  for (hipStream_t s : {c->stream, c->h2d_stream, c->d2h_stream, c->aux_stream, c->q0_stream})
     if (s && !dev_ok(c, hipStreamSynchronize(s), "sync")) return CDA_E_DEVICE;
   return dev_ok(c, hipHostUnregister(p), "hipHostUnregister") ? CDA_OK : CDA_E_DEVICE;
   CDA_API_CATCH(c)

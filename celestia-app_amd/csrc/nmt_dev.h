@@ -213,15 +213,19 @@ __device__ __forceinline__ void leaf_record(const uint4* sh, const uint32_t (&A)
 }
 
 // One EDS cell `gid` (= blk * w^2 + r * w + c) of a batch: push-order check against
-// its Q0 right / lower neighbours, then its 96-B leaf record.
+// its Q0 right / lower neighbours, then its 96-B leaf record.  With ods (the contiguous k x k ODS blocks, optional) a
+// Q0 cell and its neighbours are read from there (rows k shares apart) and Q0 of eds is not read at all.
 __device__ __forceinline__ void leaf_cell(const uint8_t* __restrict__ eds, uint4* __restrict__ nodes,
-                                          unsigned long long* __restrict__ status, int k, int log2w, uint32_t gid) {
+                                          unsigned long long* __restrict__ status, int k, int log2w, uint32_t gid,
+                                          const uint8_t* __restrict__ ods = nullptr) {
   const int w = 1 << log2w;
   const uint32_t cell = gid & ((1u << (2 * log2w)) - 1);
   const uint32_t blk = gid >> (2 * log2w);
   const int r = (int)(cell >> log2w), c = (int)(cell & (w - 1));
   const bool q0 = (r < k) && (c < k);
-  const uint4* sh = reinterpret_cast<const uint4*>(eds + (size_t)gid * CDA_SHARE);
+  const bool from_ods = ods && q0;
+  const uint4* sh = reinterpret_cast<const uint4*>(
+      from_ods ? ods + ((size_t)blk * k * k + (size_t)r * k + c) * CDA_SHARE : eds + (size_t)gid * CDA_SHARE);
 
   uint32_t A[16];
   load16(sh, A);
@@ -230,7 +234,7 @@ __device__ __forceinline__ void leaf_cell(const uint8_t* __restrict__ eds, uint4
       unsigned long long key = ((unsigned long long)CDA_AXIS_ROW << 40) | ((unsigned long long)r << 20) | (c + 1);
       atomicMin(status + blk, key);
     }
-    if (r + 1 < k && ns_below(sh + (size_t)w * (CDA_SHARE / 16), A)) {
+    if (r + 1 < k && ns_below(sh + (size_t)(from_ods ? k : w) * (CDA_SHARE / 16), A)) {
       unsigned long long key = ((unsigned long long)CDA_AXIS_COL << 40) | ((unsigned long long)c << 20) | (r + 1);
       atomicMin(status + blk, key);
     }

@@ -33,10 +33,10 @@ namespace cda {
 
 __global__ void __launch_bounds__(256) leaf_hash_kernel(const uint8_t* __restrict__ eds, uint4* __restrict__ nodes,
                                                         unsigned long long* __restrict__ status, int k, int log2w,
-                                                        uint32_t total_cells) {
+                                                        uint32_t total_cells, const uint8_t* __restrict__ ods) {
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= total_cells) return;
-  leaf_cell(eds, nodes, status, k, log2w, gid);
+  leaf_cell(eds, nodes, status, k, log2w, gid, ods);
 }
 
 // One thread per output node. Level 1 reads leaf records in cell-major layout
@@ -574,13 +574,13 @@ __global__ void __launch_bounds__(256) axes_leaf_kernel(const uint8_t* __restric
 // launchers
 // ---------------------------------------------------------------------------
 int launch_leaf_hash(const uint8_t* d_eds, void* d_leaf_nodes, unsigned long long* d_status, int k, int nblocks,
-                     hipStream_t s) {
+                     hipStream_t s, const uint8_t* d_ods) {
   const int w = 2 * k;
   const int log2w = ilog2i(w);
   const uint32_t total = (uint32_t)nblocks * (uint32_t)w * (uint32_t)w;
   const uint32_t grid = (total + 255) / 256;
   hipLaunchKernelGGL(leaf_hash_kernel, dim3(grid), dim3(256), 0, s, d_eds, (uint4*)d_leaf_nodes, d_status, k,
-                     log2w, total);
+                     log2w, total, d_ods);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -233,6 +233,7 @@ struct Rs8RegArgs {
   long long cpy_blk, cpy_cw, cpy_sh;
   int k, groups_per_blk, slices;
   int remap;  // XCD-contiguous workgroup order
+  int pair;   // the launch carries a second descriptor (launch_rs_encode8_pair)
 };
 
 // ===========================================================================
@@ -563,15 +564,55 @@ __device__ __forceinline__ void rs_g2_body(const Rs8RegArgs& a, int wg, uint4* x
 }
 
 template <int L>
-__global__ void __launch_bounds__(64 << (L - 4), 4) rs_encode8_g2_kernel(Rs8RegArgs a) {
+__global__ void __launch_bounds__(64 << (L - 4), 4) rs_encode8_g2_kernel(Rs8RegArgs a, Rs8RegArgs a2) {
   extern __shared__ __attribute__((aligned(16))) uint4 xbuf[];
   // XCD-contiguous work (a.remap): the dispatcher deals workgroups to the 8 XCDs round-robin, so XCD x runs blocks
   // x, x + 8, ...; map them to one contiguous range of codeword pairs per XCD
   const unsigned g = gridDim.x, b = blockIdx.x;
-  const int wg = (a.remap && (g % 8u) == 0) ? (int)((b % 8u) * (g / 8u) + b / 8u) : (int)b;
+  int wg = (a.remap && (g % 8u) == 0) ? (int)((b % 8u) * (g / 8u) + b / 8u) : (int)b;
   // (static issue priority, s_setprio 1, for the second half of the waves: columns 0.857 vs 0.839 ms per B = 128
   // step in a rotating same-box A/B, profiles/r05_prio_ab.log; not kept)
-  rs_g2_body<L>(a, wg, xbuf);
+  // Two jobs in one grid (a.pair; both of slices == 1 and the same groups_per_blk), block-major: a block's workgroups
+  // of job a, then its workgroups of job a2.  The choice is wave-uniform (a scalar select of the descriptor); no
+  // workgroup waits on another.
+  bool second = false;
+  if (a.pair) {
+    const int gpb = a.groups_per_blk, blk = wg / (2 * gpb), rem = wg - blk * 2 * gpb;
+    second = rem >= gpb;
+    wg = blk * gpb + (second ? rem - gpb : rem);
+  }
+  // field by field: a select between the two descriptors' addresses would put both into scratch
+  Rs8RegArgs j = a;
+  j.src = second ? a2.src : a.src;
+  j.src_blk = second ? a2.src_blk : a.src_blk;
+  j.src_cw = second ? a2.src_cw : a.src_cw;
+  j.src_sh = second ? a2.src_sh : a.src_sh;
+  j.dst = second ? a2.dst : a.dst;
+  j.dst_blk = second ? a2.dst_blk : a.dst_blk;
+  j.dst_cw = second ? a2.dst_cw : a.dst_cw;
+  j.dst_sh = second ? a2.dst_sh : a.dst_sh;
+  rs_g2_body<L>(j, wg, xbuf);
+}
+
+// Q0 of the EDS from the ODS (the block path's copy beside the hashing, engine.cpp): chunks of 1024 uint4, 16 B per
+// lane and step, four steps a workgroup apart; a grid smaller than the chunk count walks them grid-stride.  One ODS
+// row is 2^log2row uint4; EDS rows are twice as long.
+__global__ void __launch_bounds__(256) rs_q0_copy_kernel(const uint4* __restrict__ ods, uint4* __restrict__ eds,
+                                                         int log2row, int log2k, unsigned long long total) {
+  for (unsigned long long chunk = blockIdx.x; chunk * 1024 < total; chunk += gridDim.x) {
+    const unsigned long long i0 = chunk * 1024 + threadIdx.x;
+    uint4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if (i0 + q * 256 < total) v[q] = ods[i0 + q * 256];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const unsigned long long i = i0 + q * 256;
+      if (i >= total) continue;
+      const unsigned long long row = i >> log2row, blk = row >> log2k, r = row & ((1ull << log2k) - 1);
+      eds[((((blk << (log2k + 1)) + r) << (log2row + 1))) + (i & ((1ull << log2row) - 1))] = v[q];
+    }
+  }
 }
 
 static Rs8RegArgs reg_args(const RsJob& j);
@@ -638,34 +679,75 @@ static Rs8RegArgs reg_args(const RsJob& j) {
   return r;
 }
 
-int launch_rs_encode8(const RsJob& j, hipStream_t s) {
-  if (j.k < 1 || j.k > 128 || j.shard_len % 64 != 0) return -2;
-  const int L = ilog2(j.k);
-  // Latency launches: when the register encoder's grid would leave most CUs idle (one block: 64 / 128 workgroups
-  // for rows / columns at k = 128, a consensus band 16), the LDS encoder splits each codeword's bytes over
-  // workgroups of U units (32 B each) instead, so the pass spreads over the chip.  CDA_RS8_LAT_U picks U
-  // (0 = off; default 4); results are identical either way (both encoders are bit-exact).
+// Latency launches: when the register encoder's grid would leave most CUs idle (one block: 64 / 128 workgroups
+// for rows / columns at k = 128, a consensus band 16), the LDS encoder splits each codeword's bytes over
+// workgroups of U units (32 B each) instead, so the pass spreads over the chip.  CDA_RS8_LAT_U picks U
+// (0 = off; default 4); results are identical either way (both encoders are bit-exact).
+static int rs8_lat_u() {
   static const int lat_u = [] {
     const char* e = CDA_AB_ENV("CDA_RS8_LAT_U");
     const int v = e ? atoi(e) : 4;
     return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
   }();
+  return lat_u;
+}
+static bool rs8_lat(const RsJob& j) {
+  const int lat_u = rs8_lat_u();
   const long long g2_grid = (long long)j.nblk * (j.cw_per_blk / 2) * (j.shard_len / 512);
-  const bool lat = lat_u && L >= 4 && j.shard_len % (32 * lat_u) == 0 && g2_grid < 32;
+  return lat_u && ilog2(j.k) >= 4 && j.shard_len % (32 * lat_u) == 0 && g2_grid < 32;
+}
+
+bool rs8_reg_batched(const RsJob& j) {
+  return j.k >= 1 && j.k <= 128 && ilog2(j.k) >= 4 && !rs8_lat(j) && j.k % 2 == 0 && j.cw_per_blk % 2 == 0 &&
+         j.shard_len > 0 && j.shard_len % 512 == 0;
+}
+
+// rs_encode8_g2_kernel over grid workgroups of the body for m = 2^L
+static int launch_g2(int L, long long grid, const Rs8RegArgs& r, const Rs8RegArgs& r2, hipStream_t s) {
+  if (grid <= 0 || grid > 0x7FFFFFFF) return -2;
+  const size_t lds = L > 4 ? (size_t)(1 << L) * 32 * 16 : 0;
+  const dim3 block(64 << (L - 4));
+  switch (L) {
+    case 4: hipLaunchKernelGGL(rs_encode8_g2_kernel<4>, dim3((unsigned)grid), block, lds, s, r, r2); break;
+    case 5: hipLaunchKernelGGL(rs_encode8_g2_kernel<5>, dim3((unsigned)grid), block, lds, s, r, r2); break;
+    case 6: hipLaunchKernelGGL(rs_encode8_g2_kernel<6>, dim3((unsigned)grid), block, lds, s, r, r2); break;
+    default: hipLaunchKernelGGL(rs_encode8_g2_kernel<7>, dim3((unsigned)grid), block, lds, s, r, r2); break;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_rs_encode8_pair(const RsJob& ja, const RsJob& jb, bool remap, hipStream_t s) {
+  if (!rs8_reg_batched(ja) || !rs8_reg_batched(jb) || ja.shard_len != 512 || jb.shard_len != 512 || ja.k != jb.k ||
+      ja.cw_per_blk != jb.cw_per_blk || ja.nblk != jb.nblk || ja.cpy || jb.cpy)
+    return -2;
+  Rs8RegArgs r = reg_args(ja);
+  const Rs8RegArgs r2 = reg_args(jb);
+  r.remap = remap;
+  r.pair = 1;
+  return launch_g2(ilog2(ja.k), 2ll * ja.nblk * r.groups_per_blk, r, r2, s);
+}
+
+int launch_q0_copy(const uint8_t* d_ods, uint8_t* d_eds, int k, int nblocks, int max_wgs, hipStream_t s) {
+  if (k < 1 || (k & (k - 1)) || nblocks < 1) return -2;
+  const int log2k = ilog2(k);
+  const unsigned long long total = (unsigned long long)nblocks * k * k * (CDA_SHARE / 16);
+  unsigned long long grid = (total + 1023) / 1024;
+  if (max_wgs > 0 && grid > (unsigned long long)max_wgs) grid = max_wgs;
+  if (grid > 0x7FFFFFFFull) return -2;
+  hipLaunchKernelGGL(rs_q0_copy_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const uint4*)d_ods, (uint4*)d_eds,
+                     log2k + 5, log2k, total);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_rs_encode8(const RsJob& j, hipStream_t s) {
+  if (j.k < 1 || j.k > 128 || j.shard_len % 64 != 0) return -2;
+  const int L = ilog2(j.k);
+  const int lat_u = rs8_lat_u();
+  const bool lat = rs8_lat(j);
   // Batched path: 2 codewords per workgroup, register-resident (k >= 16).
-  if (!lat && L >= 4 && j.k % 2 == 0 && j.cw_per_blk % 2 == 0 && j.shard_len % 512 == 0) {
+  if (rs8_reg_batched(j)) {
     const Rs8RegArgs r = reg_args(j);
-    const long long grid = (long long)j.nblk * r.groups_per_blk * r.slices;
-    if (grid <= 0 || grid > 0x7FFFFFFF) return -2;
-    const size_t lds = L > 4 ? (size_t)(1 << L) * 32 * 16 : 0;
-    const dim3 block(64 << (L - 4));
-    switch (L) {
-      case 4: hipLaunchKernelGGL(rs_encode8_g2_kernel<4>, dim3((unsigned)grid), block, lds, s, r); break;
-      case 5: hipLaunchKernelGGL(rs_encode8_g2_kernel<5>, dim3((unsigned)grid), block, lds, s, r); break;
-      case 6: hipLaunchKernelGGL(rs_encode8_g2_kernel<6>, dim3((unsigned)grid), block, lds, s, r); break;
-      default: hipLaunchKernelGGL(rs_encode8_g2_kernel<7>, dim3((unsigned)grid), block, lds, s, r); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_g2(L, (long long)j.nblk * r.groups_per_blk * r.slices, r, r, s);
   }
   // General path (any k <= 128, any shard length, single codewords): LDS-resident.
   Rs8Args a;

@@ -2,7 +2,7 @@
 # A/B/... of library builds on one box: short bench runs (no extras) in a rotating order so that run position
 # (clock / thermal drift) does not favour one build; prints each run and the per-build means of the kernel times.
 # usage: scripts/ab_bench.sh <rounds> <lib.so>[@VAR=value] [<lib.so>[@VAR=value] ...]
-#   (lib.so@VAR=value: that build with VAR=value in the environment, for the knobs of the hooks build)
+#   (lib.so@VAR=value[,VAR2=value2]: that build with these in the environment, for the knobs of the hooks build)
 set -u
 N=$1; shift
 LIBS=("$@")
@@ -13,7 +13,7 @@ mkdir -p gpurun_out
 for i in $(seq 0 $((N - 1))); do
   for j in $(seq 0 $((M - 1))); do
     lib=${LIBS[$(((i + j) % M))]}
-    path=${lib%%@*}; envs=(); [ "$path" != "$lib" ] && envs=("${lib#*@}")
+    path=${lib%%@*}; envs=(); [ "$path" != "$lib" ] && IFS=, read -ra envs <<< "${lib#*@}"
     env "${envs[@]}" CDA_LIB=$path timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline --no-k512-split > "$RUN_LOG" 2>&1 || exit 1
     python3 -c "
 import json
