@@ -62,7 +62,7 @@ EXPORTS = [
     "cda_square_open_eds", "cda_befp_validate", "cda_befp_validate_device",
     "cda_samples_assemble_device", "cda_square_open_eds_device", "cda_square_rebuild",
     "cda_commitment_proof_sizes", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
-    "cda_commitment_proofs_verify_device",
+    "cda_commitment_proofs_verify_device", "cda_square_index", "cda_square_read",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -138,6 +138,25 @@ class CommitmentProofDesc(ctypes.Structure):
                 ("subtree_root_threshold", ctypes.c_uint32), ("ns", ctypes.c_uint8 * 29), ("pad_", ctypes.c_uint8 * 3)]
 
 
+class Sequence(ctypes.Structure):
+    """cda_sequence: one sequence of a retained square (cda_square_index)."""
+    _fields_ = [("start", ctypes.c_uint32), ("nshares", ctypes.c_uint32), ("seq_len", ctypes.c_uint32),
+                ("kind", ctypes.c_uint8), ("share_version", ctypes.c_uint8), ("status", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8), ("ns", ctypes.c_uint8 * 29), ("pad2_", ctypes.c_uint8 * 3)]
+
+
+class SquareSummary(ctypes.Structure):
+    """cda_square_summary: what cda_square_index counted."""
+    _fields_ = [("k", ctypes.c_uint32), ("nseq", ctypes.c_uint32), ("npadding", ctypes.c_uint32),
+                ("norphans", ctypes.c_uint32), ("first_orphan", ctypes.c_uint32)]
+
+
+class SequenceRange(ctypes.Structure):
+    """cda_sequence_range: one query of cda_square_read."""
+    _fields_ = [("start", ctypes.c_uint32), ("nshares", ctypes.c_uint32), ("seq_len", ctypes.c_uint32),
+                ("compact", ctypes.c_uint32)]
+
+
 class NamespaceQuery(ctypes.Structure):
     """cda_namespace_query: tree (axis, index).ProveNamespace(ns)."""
     _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("ns", ctypes.c_uint8 * 29),
@@ -194,6 +213,14 @@ CP_VALID, CP_MALFORMED, CP_ROW_COUNT, CP_RANGE, CP_ALIGNMENT, CP_ROOT_COUNT, CP_
     CP_SUBTREE_ROOTS, CP_COMMITMENT = range(10)
 
 # the same records as numpy rows (whole batches are built as arrays)
+# cda_sequence's kind and status bits (include/cda.h CDA_SEQ_*)
+SEQ_KIND_TX, SEQ_KIND_PFB, SEQ_KIND_BLOB = 0, 1, 2
+SEQ_TRUNCATED, SEQ_BROKEN, SEQ_VERSION, SEQ_RESERVED_NS, SEQ_UNALIGNED = 1, 2, 4, 8, 16
+NO_SHARE = 0xFFFFFFFF
+SEQUENCE_DTYPE = np.dtype([("start", "<u4"), ("nshares", "<u4"), ("seq_len", "<u4"), ("kind", "u1"),
+                           ("share_version", "u1"), ("status", "u1"), ("pad_", "u1"), ("ns", "u1", (29,)),
+                           ("pad2_", "u1", (3,))])
+SEQUENCE_RANGE_DTYPE = np.dtype([("start", "<u4"), ("nshares", "<u4"), ("seq_len", "<u4"), ("compact", "<u4")])
 BLOB_RANGE_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4")])
 COMMITMENT_ROW_DTYPE = np.dtype([("nmt_start", "<i4"), ("nmt_end", "<i4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("root_off", "<u4"), ("nroots", "<u4"), ("total", "<i8"), ("index", "<i8"),
@@ -320,6 +347,8 @@ def lib(path=None, older=False):
                                                          P]),
                 "cda_commitment_proofs_verify_device": (I32, [P, U32, P, P, P, P, U32, P, U32, P, U32, P, U32, P, U32,
                                                                 P, U32, P, P]),
+                "cda_square_index": (I32, [P, U32, U32, P, P, P]),
+                "cda_square_read": (I32, [P, U32, P, P, U64, P]),
             }
             for name, (res, args) in sig.items():
                 if older and not hasattr(L, name):
@@ -1083,6 +1112,57 @@ class Square:
         cda.commitment.CommitmentProof; namespaces: the 29-byte namespace of each blob."""
         from . import commitment as C
         return C.proofs_from_raw(self.commitment_proofs_raw(ranges, threshold), namespaces)
+
+    def index(self, threshold=64, commitments=True, cap=None):
+        """cda_square_index: every sequence of the square (the two compact ones and the blobs) in ascending order
+        -> (SEQUENCE_DTYPE rows, (nseq, 32) uint8 share commitments or None, summary dict).  A blob whose status is
+        not 0 has a commitment of zeros.  cap: records offered at first; if the square has more, one more call."""
+        cap = 256 if cap is None else int(cap)
+        while True:
+            seqs = np.zeros(cap, SEQUENCE_DTYPE)
+            com = np.zeros((cap, 32), np.uint8) if commitments else None
+            summary = SquareSummary()
+            rc = self._ctx._L.cda_square_index(self._h, threshold, cap, _p(seqs), _p(com), ctypes.byref(summary))
+            _check(rc, ctx=self._ctx)
+            if summary.nseq <= cap:
+                break
+            cap = summary.nseq
+        n = summary.nseq
+        info = {name: int(getattr(summary, name)) for name, _ in SquareSummary._fields_}
+        return seqs[:n], (com[:n] if commitments else None), info
+
+    @staticmethod
+    def sequence_ranges(seqs):
+        """SEQUENCE_DTYPE rows, or (start, nshares, seq_len, compact) tuples -> SEQUENCE_RANGE_DTYPE rows."""
+        if isinstance(seqs, np.ndarray) and seqs.dtype == SEQUENCE_RANGE_DTYPE:
+            return np.ascontiguousarray(seqs)
+        if isinstance(seqs, np.ndarray) and seqs.dtype == SEQUENCE_DTYPE:
+            q = np.zeros(len(seqs), SEQUENCE_RANGE_DTYPE)
+            for name in ("start", "nshares", "seq_len"):
+                q[name] = seqs[name]
+            q["compact"] = seqs["kind"] != SEQ_KIND_BLOB
+            return q
+        return np.array([tuple(int(v) for v in x) for x in seqs], SEQUENCE_RANGE_DTYPE).reshape(-1)
+
+    def read(self, seqs):
+        """cda_square_read: the payload of every sequence, share headers stripped -> list of bytes."""
+        q = self.sequence_ranges(seqs)
+        lens = q["seq_len"].astype(np.uint64)
+        off = np.zeros(len(q) + 1, np.uint64)
+        np.cumsum(lens, out=off[1:])
+        data = np.zeros(max(1, int(off[-1])), np.uint8)
+        rc = self._ctx._L.cda_square_read(self._h, len(q), _p(q), _p(off), int(off[-1]), _p(data))
+        _check(rc, ctx=self._ctx)
+        return [data[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(q))]
+
+    def read_device(self, seqs, data_off, data_cap, d_data):
+        """cda_square_read with the payloads at the device address d_data: query q at [data_off[q], + seq_len)."""
+        q = self.sequence_ranges(seqs)
+        off = np.ascontiguousarray(data_off, np.uint64)
+        if len(off) < len(q):
+            raise ValueError("one offset per sequence")
+        rc = self._ctx._L.cda_square_read(self._h, len(q), _p(q), _p(off), int(data_cap), ctypes.c_void_p(d_data))
+        _check(rc, ctx=self._ctx)
 
     @staticmethod
     def namespace_queries(queries):

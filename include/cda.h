@@ -514,6 +514,57 @@ int cda_commitment_proofs_verify_device(cda_ctx* ctx, uint32_t nproofs, const vo
                                         const void* d_data_roots, uint32_t nroots, const void* d_commitments,
                                         uint32_t ncommitments, void* d_verdicts, void* stream);
 
+/* ---- what is in a retained square: its sequences (the two compact ones and the blobs) read back from the shares,
+ * the blobs' share commitments, and the payload bytes with the share headers stripped (celestia-node's
+ * blob.Get / GetAll / GetProof / Included start here).  Parity unpinned: go-square's shares package is not in the
+ * reference tree; the rule (csrc/share_index_rule.h) restates specs/src/specs/shares.md and namespace.md. ---- */
+enum { CDA_SEQ_KIND_TX = 0, CDA_SEQ_KIND_PFB = 1, CDA_SEQ_KIND_BLOB = 2 };
+/* Status of a sequence: a bit mask, every bit that applies.  A hostile square gives statuses, never an error code. */
+enum {
+  CDA_SEQ_TRUNCATED = 1,   /* start + nshares > k^2 */
+  CDA_SEQ_BROKEN = 2,      /* inside its claim: another start share (padding or not), or a continuation share of
+                              another namespace or share version */
+  CDA_SEQ_VERSION = 4,     /* share version != 0 */
+  CDA_SEQ_RESERVED_NS = 8, /* a blob in a primary (version 0, id <= 255) or secondary (version 255) reserved namespace */
+  CDA_SEQ_UNALIGNED = 16,  /* a blob with W = SubTreeWidth(nshares, threshold) > k or start % W != 0: no commitment
+                              exists for it in this square (not looked at when the threshold is 0) */
+};
+typedef struct {
+  uint32_t start, nshares; /* claimed extent [start, start + nshares) of the ODS, row-major */
+  uint32_t seq_len;        /* payload bytes */
+  uint8_t kind, share_version, status, pad_;
+  uint8_t ns[29];
+  uint8_t pad2_[3];
+} cda_sequence; /* 48 B */
+typedef struct {
+  uint32_t k, nseq, npadding, norphans, first_orphan; /* first_orphan 0xFFFFFFFF: none */
+} cda_square_summary;
+#ifdef __cplusplus
+static_assert(sizeof(cda_sequence) == 48 && sizeof(cda_square_summary) == 20, "record sizes are part of the ABI");
+#else
+_Static_assert(sizeof(cda_sequence) == 48 && sizeof(cda_square_summary) == 20, "record sizes are part of the ABI");
+#endif
+/* Every sequence of a retained square in ascending order, and (commitments != NULL) the share commitment of every
+ * blob whose status is 0 under subtree_root_threshold, from the retained tree nodes (GetCommitment); every other
+ * record's commitment is 32 zero bytes.  Writes min(nseq, cap) records (and commitments); summary->nseq is the count.
+ * An orphan is a continuation share with no start share before it, after a padding share or past its sequence's claim:
+ * counted, the first one reported, part of no sequence.  seqs and commitments may be host or device memory (seqs may be
+ * NULL when cap is 0); summary is host memory.  seqs and commitments are written after the commitments were computed
+ * and summary last, on success only: a call that fails there or earlier leaves all three as they were.  CDA_E_ARG
+ * before any launch for a null handle or summary, or subtree_root_threshold == 0 when commitments are asked for. */
+int cda_square_index(cda_square* sq, uint32_t subtree_root_threshold, uint32_t cap, cda_sequence* seqs,
+                     uint8_t* commitments, cda_square_summary* summary);
+typedef struct {
+  uint32_t start, nshares, seq_len, compact; /* a cda_sequence's extent and length; compact: kind is TX or PFB */
+} cda_sequence_range;
+/* Payloads of nq sequences, headers stripped (34 B of a blob's first share and 30 B of its later ones; 38 B and 34 B of
+ * a compact sequence's), query q at data[data_off[q], + seq_len).  No byte outside those ranges is written;
+ * overlapping ranges are the caller's business.  q and data_off are host memory, data host or device memory.
+ * CDA_E_ARG before any launch for a null handle, start + nshares > k^2, nshares smaller than seq_len needs, or
+ * data_off[q] + seq_len > data_cap. */
+int cda_square_read(cda_square* sq, uint32_t nq, const cda_sequence_range* q, const uint64_t* data_off,
+                    uint64_t data_cap, uint8_t* data);
+
 /* ---- namespace data with completeness proofs: nmt ProveNamespace / Proof.VerifyNamespace, batched ---- */
 /* "Everything of namespace ns in tree (axis, index), and a proof that nothing was withheld."  Namespaces compare as
  * 29-byte big-endian strings; leaf i's namespace is the share's own in Q0 and 0xFF x 29 elsewhere. */
