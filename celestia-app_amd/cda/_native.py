@@ -63,6 +63,8 @@ EXPORTS = [
     "cda_samples_assemble_device", "cda_square_open_eds_device", "cda_square_rebuild",
     "cda_commitment_proof_sizes", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
     "cda_commitment_proofs_verify_device", "cda_square_index", "cda_square_read",
+    "cda_square_axis_halves", "cda_axis_halves_verify", "cda_axis_halves_verify_device",
+    "cda_axis_halves_assemble_device", "cda_square_rebuild_axes",
 ]
 
 OPT_HUGE_PAGES = 1
@@ -200,6 +202,17 @@ class SampleDesc(ctypes.Structure):
 # the per-sample statuses of an assembled square (include/cda.h CDA_SAMPLE_*)
 SAMPLE_PLACED, SAMPLE_DUPLICATE, SAMPLE_CONFLICT, SAMPLE_REJECTED, SAMPLE_MALFORMED = range(5)
 
+
+class AxisHalfDesc(ctypes.Structure):
+    """cda_axis_half_desc: k consecutive cells of a row or a column, cells [side k, side k + k)."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("side", ctypes.c_uint32),
+                ("root_off", ctypes.c_uint32)]
+
+
+# which half of the axis (include/cda.h CDA_SIDE_*), and the per-half statuses (CDA_HALF_*)
+SIDE_FIRST, SIDE_SECOND = 0, 1
+HALF_PLACED, HALF_DUPLICATE, HALF_CONFLICT, HALF_BAD_ROOT, HALF_MALFORMED = range(5)
+
 # cda_namespace_result.kind (include/cda.h CDA_NSP_*), and "no leaf hash" of a cda_nmt_ns_proof_desc
 NSP_EMPTY, NSP_INCLUSION, NSP_ABSENCE = range(3)
 NO_LEAF_HASH = 0xFFFFFFFF
@@ -246,6 +259,7 @@ BEFP_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("entry_off", "<u
 BEFP_ENTRY_DTYPE = np.dtype([("pos", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4")])
 SAMPLE_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("pos", "<u4"), ("node_off", "<u4"),
                               ("nnodes", "<u4")])
+AXIS_HALF_DESC_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("side", "<u4"), ("root_off", "<u4")])
 RANGE_QUERY_DTYPE = np.dtype([("axis", "<u4"), ("index", "<u4"), ("start", "<u4"), ("end", "<u4")])
 NMT_PROOF_DESC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("node_off", "<u4"), ("nnodes", "<u4"),
                                  ("leaf_off", "<u4"), ("root", "<u4")])
@@ -349,6 +363,11 @@ def lib(path=None, older=False):
                                                                 P, U32, P, P]),
                 "cda_square_index": (I32, [P, U32, U32, P, P, P]),
                 "cda_square_read": (I32, [P, U32, P, P, U64, P]),
+                "cda_square_axis_halves": (I32, [P, U32, P, P, U64]),
+                "cda_axis_halves_verify": (I32, [P, U32, U32, P, P, P, U32, P, P]),
+                "cda_axis_halves_verify_device": (I32, [P, U32, U32, P, P, P, U32, P, P, P]),
+                "cda_axis_halves_assemble_device": (I32, [P, U32, U32, P, P, P, P, P, P, P]),
+                "cda_square_rebuild_axes": (I32, [P, U32, U32, P, P, P, P, ctypes.POINTER(P), P, P, P, P, P]),
             }
             for name, (res, args) in sig.items():
                 if older and not hasattr(L, name):
@@ -901,6 +920,71 @@ class Context:
         _check(rc, err, self)
         return sq
 
+    # ---- halves of rows and columns ----
+    def axis_halves_verify(self, k, descs, shares, roots, want_axes=False):
+        """cda_axis_halves_verify: batched Row.Verify of halves of 2k x 2k squares.  descs: AXIS_HALF_DESC_DTYPE rows;
+        shares (nhalves, k, 512); roots (n, 90), per block the 2k row roots then the 2k column roots, all uint8.
+        -> statuses (nhalves,) uint8, HALF_* codes[, axes (nhalves, 2k, 512)]."""
+        descs = np.ascontiguousarray(descs, AXIS_HALF_DESC_DTYPE)
+        n = len(descs)
+        shares = np.ascontiguousarray(shares, np.uint8).reshape(n, k, SHARE_SIZE)
+        roots = np.ascontiguousarray(roots, np.uint8).reshape(-1, NODE_SIZE)
+        statuses = np.full(n, HALF_MALFORMED, np.uint8)
+        axes = np.zeros((n, 2 * k, SHARE_SIZE), np.uint8) if want_axes else None
+
+        def p(a):
+            return _p(a) if a is not None and len(a) else None
+        rc = self._L.cda_axis_halves_verify(self._h, k, n, p(descs), p(shares), p(roots), len(roots), p(statuses),
+                                            p(axes))
+        _check(rc, ctx=self)
+        return (statuses, axes) if want_axes else statuses
+
+    def axis_halves_verify_device(self, k, nhalves, d_descs, d_shares, d_roots, nroots, d_statuses, d_axes=0,
+                                  stream=None):
+        """cda_axis_halves_verify_device: the same with device addresses, asynchronous on `stream`."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_axis_halves_verify_device(self._h, k, nhalves, V(d_descs), V(d_shares), V(d_roots), nroots,
+                                                   V(d_statuses), V(d_axes or None), V(stream or 0))
+        _check(rc, ctx=self)
+
+    def axis_halves_assemble_device(self, k, nhalves, d_descs, d_shares, d_roots, d_eds, d_present, d_statuses,
+                                    stream=None):
+        """cda_axis_halves_assemble_device: verify the halves of one square and place the completed axes, every
+        argument a device address, asynchronous on `stream`.  d_eds ((2k)^2 x 512 B), d_present ((2k)^2) and
+        d_statuses (nhalves, HALF_* codes) are the outputs."""
+        V = ctypes.c_void_p
+        rc = self._L.cda_axis_halves_assemble_device(self._h, k, nhalves, V(d_descs), V(d_shares), V(d_roots),
+                                                     V(d_eds), V(d_present), V(d_statuses), V(stream or 0))
+        _check(rc, ctx=self)
+
+    def square_rebuild_axes(self, descs, shares, row_roots, col_roots, want_eds=False):
+        """cda_square_rebuild_axes without raising on the two repair errors: (rc, square or None, statuses, present,
+        eds or None, err).  On CDA_E_UNREPAIRABLE / CDA_E_BYZANTINE present and eds hold the square where rsmt2d
+        stops."""
+        descs = np.ascontiguousarray(descs, AXIS_HALF_DESC_DTYPE)
+        n = len(descs)
+        row_roots = np.ascontiguousarray(row_roots, np.uint8).reshape(-1, NODE_SIZE)
+        col_roots = np.ascontiguousarray(col_roots, np.uint8).reshape(-1, NODE_SIZE)
+        w = len(row_roots)
+        if len(col_roots) != w or w % 2:
+            raise CdaError(E_ARG, "the roots are 2k row roots and 2k column roots")
+        shares = np.ascontiguousarray(shares, np.uint8).reshape(n, w // 2, SHARE_SIZE)
+        statuses = np.full(n, HALF_MALFORMED, np.uint8)
+        present = np.zeros(w * w, np.uint8)
+        eds = np.zeros((w * w, SHARE_SIZE), np.uint8) if want_eds else None
+        dah = np.empty(32, np.uint8)
+        h, err = ctypes.c_void_p(), ErrInfo()
+
+        def p(a):
+            return _p(a) if len(a) else None
+        rc = self._L.cda_square_rebuild_axes(self._h, w // 2, n, p(descs), p(shares), _p(row_roots), _p(col_roots),
+                                             ctypes.byref(h), p(statuses), _p(present), _p(eds), _p(dah),
+                                             ctypes.byref(err))
+        if rc not in (OK, E_UNREPAIRABLE, E_BYZANTINE):
+            _check(rc, err, self)
+        sq = Square._adopt(self, w // 2, h, row_roots.copy(), col_roots.copy(), dah) if rc == OK else None
+        return rc, sq, statuses, present, eds, err
+
     # ---- profiling ----
     def profile_enable(self, on=True):
         _check(self._L.cda_profile_enable(self._h, 1 if on else 0), ctx=self)
@@ -983,6 +1067,22 @@ class Square:
         rc = self._ctx._L.cda_square_prove(self._h, len(q), _p(q), max_nodes, ctypes.c_void_p(d_counts),
                                            ctypes.c_void_p(d_nodes), ctypes.c_void_p(d_shares or None), shares_cap)
         _check(rc, ctx=self._ctx)
+
+    def axis_halves(self, queries, d_shares=0, shares_cap=0):
+        """cda_square_axis_halves.  queries: (axis, index, side) tuples or AXIS_HALF_DESC_DTYPE rows.
+        -> shares (nq, k, 512) uint8, query q's k cells in cell order; with d_shares (a device address of shares_cap
+        bytes) the halves are written there instead and nothing is returned."""
+        q = queries if isinstance(queries, np.ndarray) and queries.dtype == AXIS_HALF_DESC_DTYPE else \
+            np.array([tuple(x)[:3] + (0,) for x in queries], AXIS_HALF_DESC_DTYPE)
+        q = np.ascontiguousarray(q)
+        if d_shares:
+            rc = self._ctx._L.cda_square_axis_halves(self._h, len(q), _p(q), ctypes.c_void_p(d_shares), shares_cap)
+            _check(rc, ctx=self._ctx)
+            return None
+        shares = np.zeros((len(q), self.k, SHARE_SIZE), np.uint8)
+        rc = self._ctx._L.cda_square_axis_halves(self._h, len(q), _p(q), _p(shares), shares.nbytes)
+        _check(rc, ctx=self._ctx)
+        return shares
 
     @staticmethod
     def share_proof_sizes(k, ranges):

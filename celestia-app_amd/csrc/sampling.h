@@ -323,4 +323,46 @@ int launch_sample_prep(const AssembleArgs& a, hipStream_t s);   // malformed che
 int launch_sample_claim(const AssembleArgs& a, hipStream_t s);  // owner[cell] = the lowest verified sample
 int launch_sample_place(const AssembleArgs& a, hipStream_t s);  // owners' shares -> cells; the statuses
 
+// cda_axis_halves_verify's and cda_axis_halves_assemble_device's arguments, all device memory (include/cda.h), and
+// their workspace (axis_half.cpp, axis_half_kernels.hip)
+struct AxisHalfArgs {
+  const cda_axis_half_desc* descs;
+  const uint8_t* shares;
+  const uint8_t* roots;
+  uint8_t* statuses;
+  uint8_t* eds;      // assembling only, as axis_owner below
+  uint8_t* present;
+  uint32_t k, nhalves, nroots;
+  uint32_t assembling;  // all halves belong to one square: root_off must be 0
+  // workspace.  Per half: the decoder's codeword offset and stride, the tree's axis index, its root record and status
+  // word; per half and slot j < 2k the decoder's present mask; the axis buffer [nhalves][2k][512].  Per axis of the
+  // square (rows then columns): the lowest verified half that claims it (axis_half_rule.h kHalfNoOwner: none).
+  long long* cw_off;
+  long long* cw_stride;
+  unsigned long long* axis_idx;
+  unsigned long long* status;
+  uint8_t* recs;
+  uint8_t* mask;
+  uint32_t* axis_owner;
+  uint8_t* axes;
+};
+inline void axis_half_workspace(AxisHalfArgs& a, Arena& ws) {  // the layout, from a.k, a.nhalves and a.assembling
+  const size_t n = a.nhalves;
+  a.cw_off = ws.take<long long>(n);
+  a.cw_stride = ws.take<long long>(n);
+  a.axis_idx = ws.take<unsigned long long>(n);
+  a.status = ws.take<unsigned long long>(n);
+  a.recs = ws.take<uint8_t>(n * CDA_REC_BYTES);
+  a.mask = ws.take<uint8_t>(n * 2 * a.k);
+  a.axis_owner = ws.take<uint32_t>(a.assembling ? 4 * (size_t)a.k : 0);
+}
+int launch_axis_half_prep(const AxisHalfArgs& a, hipStream_t s);     // H0; masks, offsets, axis indices
+int launch_axis_half_scatter(const AxisHalfArgs& a, hipStream_t s);  // the halves' shares -> axis buffers, zeros beside
+int launch_axis_half_combine(const AxisHalfArgs& a, hipStream_t s);  // the verdicts of H0-H2
+int launch_axis_half_claim(const AxisHalfArgs& a, hipStream_t s);    // axis_owner = the lowest verified half
+int launch_axis_half_place(const AxisHalfArgs& a, hipStream_t s);    // owners' cells -> the square; the statuses
+// nq halves out of a retained square, packed in query order (the queries were checked by the host)
+int launch_axis_half_gather(const SquareView& v, const cda_axis_half_desc* d_q, uint32_t nq, uint8_t* d_shares,
+                            hipStream_t s);
+
 }  // namespace cda

@@ -705,6 +705,65 @@ int cda_square_rebuild(cda_ctx* ctx, uint32_t k, uint32_t nsamples, const cda_sa
                        const uint8_t* col_roots, cda_square** out, uint8_t* statuses, uint8_t* present_or_null,
                        uint8_t* eds_or_null, uint8_t* dah, cda_err_info* err);
 
+/* ---- halves of rows and columns: serve, verify, rebuild (celestia-node shwap.Row / Row.Verify) ---- */
+/* Half p: the k consecutive cells [side k, side k + k) of row `index` (axis CDA_AXIS_ROW) or of column `index`
+ * (CDA_AXIS_COL) of a 2k x 2k square, sent with no proof; its shares are shares[512 k p, 512 k (p + 1)) in cell
+ * order; the roots of its block are roots[root_off, root_off + 4k) of 90 B, the 2k row roots then the 2k column
+ * roots (cda_befp_desc's layout).  The receiver completes the axis with the codec (side 0: cells [k, 2k) are the
+ * encoding of cells [0, k); side 1: cells [0, k) are decoded from exactly the cells [k, 2k)), builds the wrapper
+ * tree (squareSize k, axisIndex index; a cell's namespace is its own first 29 bytes if index < k and its position
+ * < k, else 0xFF x 29) over the 2k cells and compares its root with the committed one.  Row.Verify lives in
+ * celestia-node, outside the pinned tree: this is the library's statement of it. */
+#define CDA_SIDE_FIRST 0  /* cells [0, k) of the axis */
+#define CDA_SIDE_SECOND 1 /* cells [k, 2k) */
+typedef struct {
+  uint32_t axis, index, side, root_off;
+} cda_axis_half_desc;
+/* statuses[p], one byte per half, the first check that applies deciding; a false half is a status, never an error
+ * code.  DUPLICATE and CONFLICT occur only where a square is assembled. */
+#define CDA_HALF_PLACED 0    /* verified (what cda_axis_halves_verify returns for a half that verifies); assembling:
+                                the lowest-indexed verified half of its axis, its bytes are every cell it owns */
+#define CDA_HALF_DUPLICATE 1 /* verified, a lower-indexed verified half has the same axis (either side of it) */
+#define CDA_HALF_CONFLICT 2  /* verified and its axis's half, but at a cell owned by a lower-indexed half its bytes
+                                differ: a row tree and a column tree commit one cell differently; it still places
+                                the cells it owns */
+#define CDA_HALF_BAD_ROOT 3  /* the tree cannot be built (push order) or its root is not the committed one */
+#define CDA_HALF_MALFORMED 4 /* axis > 1, index >= 2k, side > 1 or root_off + 4k > nroots (assembling: root_off != 0):
+                                nothing is read through it */
+/* Serve: nq halves out of a retained square, packed in query order, k x 512 B each (root_off is ignored).  `shares`
+ * may be host or device memory, as cda_square_prove's outputs; shares_cap in bytes.  CDA_E_ARG if it is too small or
+ * a query lies outside the square, before anything is launched. */
+int cda_square_axis_halves(cda_square* sq, uint32_t nq, const cda_axis_half_desc* q, uint8_t* shares,
+                           uint64_t shares_cap);
+/* Batched Row.Verify: statuses[p] is CDA_HALF_PLACED (= verified), CDA_HALF_BAD_ROOT or CDA_HALF_MALFORMED.
+ * axes_or_null receives the completed axes, nhalves x 2k x 512 B (the bytes of an axis that is not verified are
+ * unspecified, but written inside its slot).  All halves of a call share k (a power of two, else CDA_E_NOT_POW2;
+ * k <= 512 and nhalves x 2k < 2^31, else CDA_E_UNSUPPORTED); they may belong to different blocks through root_off.
+ * nhalves == 0 is legal. */
+int cda_axis_halves_verify(cda_ctx* ctx, uint32_t k, uint32_t nhalves, const cda_axis_half_desc* descs,
+                           const uint8_t* shares, const uint8_t* roots, uint32_t nroots, uint8_t* statuses,
+                           uint8_t* axes_or_null);
+/* The same with every pointer in device memory (d_shares and d_axes_or_null 16-byte, the others 4-byte aligned, else
+ * CDA_E_ARG), asynchronous on `stream`; every check is made in the kernels.  Uses the context's workspace. */
+int cda_axis_halves_verify_device(cda_ctx* ctx, uint32_t k, uint32_t nhalves, const void* d_descs,
+                                  const void* d_shares, const void* d_roots, uint32_t nroots, void* d_statuses,
+                                  void* d_axes_or_null, void* stream);
+/* Verify and place, every pointer device memory, asynchronous on `stream`, as cda_samples_assemble_device: all halves
+ * belong to the one square whose roots are d_roots (4k x 90 B; root_off must be 0); d_eds ((2k)^2 x 512 B) and
+ * d_present ((2k)^2 bytes) are cleared first and receive every cell of every placed axis -- all 2k cells of the
+ * completed axis, not only the k that were sent; d_statuses (nhalves bytes) the CDA_HALF_* of every half.  d_shares
+ * and d_eds 16-byte, the others 4-byte aligned, else CDA_E_ARG.  nhalves == 0 is legal: nothing is present. */
+int cda_axis_halves_assemble_device(cda_ctx* ctx, uint32_t k, uint32_t nhalves, const void* d_descs,
+                                    const void* d_shares, const void* d_roots, void* d_eds, void* d_present,
+                                    void* d_statuses, void* stream);
+/* The whole chain from host buffers, as cda_square_rebuild: the halves are staged and assembled straight into a new
+ * handle's memory, repaired there against the given roots (rsmt2d Repair) and committed in place.  Return codes and
+ * the meaning of out / statuses / present_or_null / eds_or_null / dah / err are cda_square_rebuild's. */
+int cda_square_rebuild_axes(cda_ctx* ctx, uint32_t k, uint32_t nhalves, const cda_axis_half_desc* descs,
+                            const uint8_t* shares, const uint8_t* row_roots, const uint8_t* col_roots,
+                            cda_square** out, uint8_t* statuses, uint8_t* present_or_null, uint8_t* eds_or_null,
+                            uint8_t* dah, cda_err_info* err);
+
 /* ---- square construction on the device (go-square square.Construct + shares.ToBytes) ---- */
 /* The step before the DA path (app/prepare_proposal.go:54,65, app/process_proposal.go:121,137): the
  * host plans the layout -- which sequence or blob goes where, the PFB share indexes, the compact
