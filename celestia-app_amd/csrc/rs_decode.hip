@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "cda_internal.h"
+#include "codec_shape.h"
 #include "gf_slice.h"
 
 namespace cda {
@@ -449,34 +450,27 @@ static int upload(int device, int bits) {
   return 0;
 }
 
-static int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) l++;
-  return l;
-}
-
 }  // namespace dec
-
-constexpr int kDecMaxLds = 144 * 1024;
 
 int rs_decode_init_device_tables(int device) {
   if (device < 0 || device >= 64) return -1;
   if (dec::upload(device, 8) || dec::upload(device, 16)) return -1;
   if (hipFuncSetAttribute((const void*)dec::rs_decode_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kDecMaxLds) != hipSuccess ||
+                          kRsDecodeMaxLds) != hipSuccess ||
       hipFuncSetAttribute((const void*)dec::rs_decode_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kDecMaxLds) != hipSuccess)
+                          kRsDecodeMaxLds) != hipSuccess)
     return -1;
   return 0;
 }
 
 int launch_rs_decode(uint8_t* d_base, const long long* d_off, const long long* d_stride, const uint8_t* d_present,
                      int ncw, int k, int shard_len, hipStream_t s) {
-  if (k < 1 || k > 32768 || shard_len % 64 != 0 || ncw <= 0) return -2;
+  const RsDecodeShape sh = rs_decode_shape(k, shard_len, ncw);  // U, slices and LDS: codec_shape.h
+  if (!sh.ok) return -2;
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64) return -1;
-  const bool ff16 = 2 * k > 256;
+  const bool ff16 = sh.PL == 16;
   const dec::Tables& t = dec::g_tab[ff16][dev];
   if (!t.log_t) return -1;
   dec::DecArgs a;
@@ -488,27 +482,15 @@ int launch_rs_decode(uint8_t* d_base, const long long* d_off, const long long* d
   a.apow = t.apow;
   a.skew = t.skew;
   a.k = k;
-  a.log2m = dec::ilog2(k);
-  a.m = 1 << a.log2m;
-  a.n = 2 * a.m;
-  a.log2n = a.log2m + 1;
-  const int PL = ff16 ? 16 : 8;
-  const int unit = PL * 4;  // bytes per lane unit
-  const int units = shard_len / unit;
-  int U = 16;
-  while (U > 1 && (units % U || a.n * U > 1024)) U >>= 1;  // <= 4 derivative items per thread
-  if (a.n * U > 1024) return -2;                          // n > 1024 (k > 512): not on the device path yet
-  // A few codewords (the per-axis Decode, a short crossword batch) leave most CUs idle: split each codeword's bytes
-  // over more workgroups (fewer units each) until the launch has 512 of them -- a workgroup's latency falls with its
-  // items per thread, and the error locator it recomputes is cheap next to that.
-  while (U > 1 && (long long)ncw * (units / U) < 512) U >>= 1;
-  a.U = U;
-  a.log2U = dec::ilog2(U);
-  a.slices = units / U;
-  const size_t lds = (size_t)a.n * PL * U * 4 + (size_t)a.n * 8;
-  if (lds > (size_t)kDecMaxLds) return -2;
-  const long long grid = (long long)ncw * a.slices;
-  if (grid > 0x7FFFFFFF) return -2;
+  a.m = sh.m;
+  a.log2m = sh.log2m;
+  a.n = sh.n;
+  a.log2n = sh.log2n;
+  a.U = sh.U;
+  a.log2U = sh.log2U;
+  a.slices = sh.slices;
+  const size_t lds = sh.lds_bytes;
+  const long long grid = sh.grid;
   if (ff16)
     hipLaunchKernelGGL(dec::rs_decode_kernel<16>, dim3((unsigned)grid), dim3(256), lds, s, a);
   else

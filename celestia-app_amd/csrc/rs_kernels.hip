@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "cda_internal.h"
+#include "codec_shape.h"
 #include "gf8_const.h"
 #include "gf_slice.h"
 
@@ -639,8 +640,8 @@ int rs_init_device_tables(int device) {
   for (int i = 0; i < 256; i++) cpoly[i] = skew[i] >= 255 ? 0 : apow[skew[i]];
   for (int i = 0; i < 256; i++)
     if (cpoly[i] != kCpoly8.v[i]) return -1;  // the encoder's compile-time constants (gf8_const.h)
-  if (hipFuncSetAttribute((const void*)rs_encode8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) !=
-      hipSuccess)
+  if (hipFuncSetAttribute((const void*)rs_encode8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          kRsEncode8MaxLds) != hipSuccess)
     return -1;
   const void* g2k[4] = {(const void*)rs_encode8_g2_kernel<4>, (const void*)rs_encode8_g2_kernel<5>,
                         (const void*)rs_encode8_g2_kernel<6>, (const void*)rs_encode8_g2_kernel<7>};
@@ -679,33 +680,25 @@ static Rs8RegArgs reg_args(const RsJob& j) {
   return r;
 }
 
-// Latency launches: when the register encoder's grid would leave most CUs idle (one block: 64 / 128 workgroups
-// for rows / columns at k = 128, a consensus band 16), the LDS encoder splits each codeword's bytes over
-// workgroups of U units (32 B each) instead, so the pass spreads over the chip.  CDA_RS8_LAT_U picks U
-// (0 = off; default 4); results are identical either way (both encoders are bit-exact).
+// Latency launches (codec_shape.h rs8_lat_shape): CDA_RS8_LAT_U picks their U (0 = off; default kRs8LatU); results
+// are identical either way (both encoders are bit-exact).
 static int rs8_lat_u() {
   static const int lat_u = [] {
     const char* e = CDA_AB_ENV("CDA_RS8_LAT_U");
-    const int v = e ? atoi(e) : 4;
+    const int v = e ? atoi(e) : kRs8LatU;
     return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
   }();
   return lat_u;
 }
-static bool rs8_lat(const RsJob& j) {
-  const int lat_u = rs8_lat_u();
-  const long long g2_grid = (long long)j.nblk * (j.cw_per_blk / 2) * (j.shard_len / 512);
-  return lat_u && ilog2(j.k) >= 4 && j.shard_len % (32 * lat_u) == 0 && g2_grid < 32;
-}
 
 bool rs8_reg_batched(const RsJob& j) {
-  return j.k >= 1 && j.k <= 128 && ilog2(j.k) >= 4 && !rs8_lat(j) && j.k % 2 == 0 && j.cw_per_blk % 2 == 0 &&
-         j.shard_len > 0 && j.shard_len % 512 == 0;
+  return rs8_reg_batched_shape(j.k, j.shard_len, j.cw_per_blk, j.nblk, rs8_lat_u());
 }
 
 // rs_encode8_g2_kernel over grid workgroups of the body for m = 2^L
 static int launch_g2(int L, long long grid, const Rs8RegArgs& r, const Rs8RegArgs& r2, hipStream_t s) {
   if (grid <= 0 || grid > 0x7FFFFFFF) return -2;
-  const size_t lds = L > 4 ? (size_t)(1 << L) * 32 * 16 : 0;
+  const size_t lds = rs8_reg_lds_bytes(L);
   const dim3 block(64 << (L - 4));
   switch (L) {
     case 4: hipLaunchKernelGGL(rs_encode8_g2_kernel<4>, dim3((unsigned)grid), block, lds, s, r, r2); break;
@@ -740,14 +733,12 @@ int launch_q0_copy(const uint8_t* d_ods, uint8_t* d_eds, int k, int nblocks, int
 }
 
 int launch_rs_encode8(const RsJob& j, hipStream_t s) {
-  if (j.k < 1 || j.k > 128 || j.shard_len % 64 != 0) return -2;
-  const int L = ilog2(j.k);
-  const int lat_u = rs8_lat_u();
-  const bool lat = rs8_lat(j);
+  const RsEncode8Shape sh = rs_encode8_shape(j.k, j.shard_len, j.cw_per_blk, j.nblk, rs8_lat_u());  // codec_shape.h
+  if (!sh.ok) return -2;
   // Batched path: 2 codewords per workgroup, register-resident (k >= 16).
-  if (rs8_reg_batched(j)) {
+  if (sh.reg) {
     const Rs8RegArgs r = reg_args(j);
-    return launch_g2(L, (long long)j.nblk * r.groups_per_blk * r.slices, r, r, s);
+    return launch_g2(sh.log2m, sh.grid, r, r, s);
   }
   // General path (any k <= 128, any shard length, single codewords): LDS-resident.
   Rs8Args a;
@@ -764,20 +755,14 @@ int launch_rs_encode8(const RsJob& j, hipStream_t s) {
   a.cpy_cw = j.cpy_cw;
   a.cpy_sh = j.cpy_sh;
   a.k = j.k;
-  a.log2m = L;
-  a.m = 1 << L;
+  a.log2m = sh.log2m;
+  a.m = sh.m;
   a.cw_per_blk = j.cw_per_blk;
-  const int units = j.shard_len / 32;  // even
-  int U = lat ? lat_u : 16;
-  while (units % U) U >>= 1;
-  a.U = U;
-  a.log2U = ilog2(U);
-  a.slices = units / U;
-  a.lat = lat ? 1 : 0;
-  const size_t lds = (size_t)a.m * 8 * U * 4 + (lat ? 256 * 8 : 0);
-  const long long grid = (long long)j.nblk * j.cw_per_blk * a.slices;
-  if (grid <= 0 || grid > 0x7FFFFFFF) return -2;
-  hipLaunchKernelGGL(rs_encode8_kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
+  a.U = sh.U;
+  a.log2U = sh.log2U;
+  a.slices = sh.slices;
+  a.lat = sh.lat;
+  hipLaunchKernelGGL(rs_encode8_kernel, dim3((unsigned)sh.grid), dim3(256), sh.lds_bytes, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
