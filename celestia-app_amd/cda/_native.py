@@ -65,9 +65,11 @@ EXPORTS = [
     "cda_commitment_proofs_verify_device", "cda_square_index", "cda_square_read",
     "cda_square_axis_halves", "cda_axis_halves_verify", "cda_axis_halves_verify_device",
     "cda_axis_halves_assemble_device", "cda_square_rebuild_axes",
+    "cda_extend_commit_mixed", "cda_extend_commit_mixed_device",
 ]
 
 OPT_HUGE_PAGES = 1
+OPT_MIXED_SMALL_MAX = 2
 
 
 class ErrInfo(ctypes.Structure):
@@ -368,6 +370,8 @@ def lib(path=None, older=False):
                 "cda_axis_halves_verify_device": (I32, [P, U32, U32, P, P, P, U32, P, P, P]),
                 "cda_axis_halves_assemble_device": (I32, [P, U32, U32, P, P, P, P, P, P, P]),
                 "cda_square_rebuild_axes": (I32, [P, U32, U32, P, P, P, P, ctypes.POINTER(P), P, P, P, P, P]),
+                "cda_extend_commit_mixed": (I32, [P, U32, P, P, P, P, P, P, P]),
+                "cda_extend_commit_mixed_device": (I32, [P, U32, P, P, P, P, P, P, P]),
             }
             for name, (res, args) in sig.items():
                 if older and not hasattr(L, name):
@@ -390,6 +394,16 @@ def strerror(code):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def mixed_offsets(ks):
+    """Where block b of a mixed-size call (cda_extend_commit_mixed) starts in each packed buffer, as int64 arrays of
+    len(ks) + 1 entries (the last is the total): "ods" and "eds" in bytes; "roots" in nodes of the host form's
+    row_roots / col_roots (2k per block); "recs" in 96-B records of the device form's d_roots (4k per block: the row
+    roots, then the column roots)."""
+    k = np.asarray(ks, np.int64)
+    cum = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)  # noqa: E731
+    return {"ods": cum(k * k * SHARE_SIZE), "eds": cum(4 * k * k * SHARE_SIZE), "roots": cum(2 * k), "recs": cum(4 * k)}
 
 
 def _check(rc, err=None, ctx=None):
@@ -504,6 +518,40 @@ class Context:
         rc = self._L.cda_extend_commit_device(self._h, k, nblocks, ctypes.c_void_p(d_ods), ctypes.c_void_p(d_eds),
                                             ctypes.c_void_p(d_roots), ctypes.c_void_p(d_dah),
                                             ctypes.c_void_p(d_status), ctypes.c_void_p(stream or 0))
+        _check(rc, ctx=self)
+
+    # ---- blocks of different sizes in one call ----
+    def extend_commit_mixed(self, ods_list, want_eds=True):
+        """ods_list: (k*k, 512) arrays, any mix of sizes -> per-block lists (eds or None, row roots, column roots, dah),
+        each block as extend_commit returns it (cda_extend_commit_mixed)."""
+        blocks = [np.ascontiguousarray(o, np.uint8).reshape(-1, SHARE_SIZE) for o in ods_list]
+        ks = np.array([max(1, int(round(len(b) ** 0.5))) for b in blocks], np.uint32)
+        if any(int(k) * int(k) != len(b) for k, b in zip(ks, blocks)):
+            raise CdaError(E_NOT_SQUARE)
+        off = mixed_offsets(ks)
+        ods = np.concatenate(blocks) if blocks else np.empty((0, SHARE_SIZE), np.uint8)
+        eds = np.empty((off["eds"][-1] // SHARE_SIZE, SHARE_SIZE), np.uint8) if want_eds else None
+        rr = np.empty((off["roots"][-1], NODE_SIZE), np.uint8)
+        cr = np.empty((off["roots"][-1], NODE_SIZE), np.uint8)
+        dah = np.empty((len(blocks), 32), np.uint8)
+        err = ErrInfo()
+        rc = self._L.cda_extend_commit_mixed(self._h, len(blocks), _p(ks), _p(ods), _p(eds), _p(rr), _p(cr), _p(dah),
+                                           ctypes.byref(err))
+        _check(rc, err, self)
+        cells, roots = off["eds"] // SHARE_SIZE, off["roots"]
+        n = len(blocks)
+        return ([eds[cells[b]:cells[b + 1]] for b in range(n)] if want_eds else [None] * n,
+                [rr[roots[b]:roots[b + 1]] for b in range(n)], [cr[roots[b]:roots[b + 1]] for b in range(n)],
+                [dah[b].tobytes() for b in range(n)])
+
+    def extend_commit_mixed_device(self, ks, d_ods, d_eds, d_roots, d_dah, d_status, stream=None):
+        """cda_extend_commit_mixed_device: device addresses of buffers packed as mixed_offsets(ks) says; asynchronous
+        on `stream` (ks is read before the call returns)."""
+        ks = np.ascontiguousarray(ks, np.uint32)
+        rc = self._L.cda_extend_commit_mixed_device(self._h, len(ks), _p(ks), ctypes.c_void_p(d_ods),
+                                                  ctypes.c_void_p(d_eds), ctypes.c_void_p(d_roots),
+                                                  ctypes.c_void_p(d_dah), ctypes.c_void_p(d_status),
+                                                  ctypes.c_void_p(stream or 0))
         _check(rc, ctx=self)
 
     # ---- device-resident building blocks (pointers are device addresses) ----

@@ -66,6 +66,29 @@ def new_data_availability_header_from_shares(shares, ctx=None):
     return dah
 
 
+def new_data_availability_headers_from_shares(share_lists, ctx=None):
+    """new_data_availability_header_from_shares of every share list, in one cda_extend_commit_mixed (roots only): the
+    squares may differ in size, as those of consecutive heights do.  Same roots, hash and errors per block."""
+    ctx = ctx or N.default_context()
+    arrs = []
+    for shares in share_lists:
+        if not is_power_of_two(len(shares)):
+            raise DAError(f"number of shares is not a power of 2: got {len(shares)}")
+        k = int(round(len(shares) ** 0.5))
+        if k * k != len(shares):
+            raise N.CdaError(N.E_NOT_SQUARE)
+        arrs.append(np.stack([np.frombuffer(bytes(s), np.uint8) for s in shares]))
+    if not arrs:
+        return []
+    _, rrs, crs, hs = ctx.extend_commit_mixed(arrs, want_eds=False)
+    out = []
+    for rr, cr, h in zip(rrs, crs, hs):
+        dah = DataAvailabilityHeader(list(rr), list(cr), ctx=ctx)
+        dah._hash = h
+        out.append(dah)
+    return out
+
+
 class DataAvailabilityHeader:
     def __init__(self, row_roots=None, column_roots=None, ctx=None):
         self.row_roots = [bytes(r) for r in (row_roots or [])]

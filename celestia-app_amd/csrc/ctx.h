@@ -11,6 +11,7 @@
 
 #include "arena.h"
 #include "cda_internal.h"
+#include "mixed_route.h"
 
 namespace cda {
 struct AxisQueue;  // axisq.cpp
@@ -112,6 +113,9 @@ struct cda_ctx {
   // the library does not own -- under cgo, Go heap.  Opt in per context with cda_set_option(CDA_OPT_HUGE_PAGES, 1) or
   // CDA_HUGE_PAGES=1 at cda_init.  A caller that recycles pinned buffers (go/cda's EDS pool) never takes this path.
   bool huge_pages = false;
+  // the largest k of a mixed-size call's blocks that goes to the one-workgroup kernel (mixed.cpp): 0 (none), 1, 2, 4
+  // or 8; cda_set_option(CDA_OPT_MIXED_SMALL_MAX).  The default is the measured one.
+  int mixed_small_max = cda::kMixedSmallMaxDefault;
   // the per-axis seams (axisq.cpp): queue of concurrent Encode / Decode / Root calls, its batch slots
   cda::AxisQueue* axq = nullptr;
   // profiling

@@ -31,7 +31,7 @@
 #include <vector>
 
 #include "ctx.h"
-
+#include "small_square.h"
 
 namespace cda {
 
@@ -419,6 +419,7 @@ int cda_init(int device, cda_ctx** out) {
   else if (rs_init_device_tables(device)) fail = "rs8 tables";
   else if (rs16_init_device_tables(device)) fail = "rs16 tables";
   else if (rs_decode_init_device_tables(device)) fail = "decode tables";
+  else if (small_square_init(device)) fail = "small-square tables";
   if (fail) {
     fprintf(stderr, "cda_init: %s initialisation failed: %s\n", fail, hipGetErrorString(hipGetLastError()));
     return CDA_E_DEVICE;
@@ -539,6 +540,10 @@ int cda_set_option(cda_ctx* c, int option, int64_t value) {
   Lock l(c);
   switch (option) {
     case CDA_OPT_HUGE_PAGES: c->huge_pages = value != 0; return CDA_OK;
+    case CDA_OPT_MIXED_SMALL_MAX:
+      if (!mixed_small_max_valid(value)) return CDA_E_ARG;
+      c->mixed_small_max = (int)value;
+      return CDA_OK;
     default: return CDA_E_ARG;
   }
   CDA_API_CATCH(c)

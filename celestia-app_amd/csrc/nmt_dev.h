@@ -666,4 +666,66 @@ __device__ __forceinline__ void rfc_level_wide(const uint32_t* src, uint32_t* ds
   }
 }
 
+
+// ---------------------------------------------------------------------------
+// DAH fold (nmt_kernels.hip dah_kernel / dah_tree_kernel / dah_wide_kernel / trees_lds_kernel, small_square_kernels.hip)
+// ---------------------------------------------------------------------------
+// RFC-6962 levels over the n leaf digests at sdig ([n + (n+1)/2][8] words of LDS, the first n filled), by the
+// calling workgroup (>= 128 threads); the 32-B hash goes to out.  Wide levels a node per thread (rfc_level_wide).  Once
+// a level has at most 64 nodes (its chain of dependent compressions is the latency), wave 0 hashes block 0 of each
+// node while wave 1 expands the node's second message block into kw (64 x kKwStride words of LDS), and the second
+// compression then runs its rounds alone.  NODES: every level's digests also go to nodes_out as bytes, level by level
+// after the n leaf digests the caller wrote there (the tree cda_extend_commit_nodes exports as dah_nodes); without
+// it the code is what it was.
+template <bool NODES = false>
+__device__ __forceinline__ void dah_fold_kw(uint32_t* sdig, int n, uint32_t* out, uint32_t* kw,
+                                            uint32_t* nodes_out = nullptr) {
+  uint32_t* src = sdig;
+  uint32_t* dst = sdig + n * 8;
+  size_t base = (size_t)n;  // NODES: nodes of the levels below the one being written
+  for (int cnt = n; cnt > 1;) {
+    const int out_cnt = (cnt + 1) >> 1;
+    if (out_cnt > 64) {
+      rfc_level_wide(src, dst, cnt, nullptr);
+    } else {
+      // every lane of waves 0 and 1 computes, with full exec masks (lanes past the level's pairs hash stale,
+      // in-bounds LDS words and store nothing), as in trees_lds_kernel
+      const int i = threadIdx.x & 63;
+      const bool pair = i < out_cnt && 2 * i + 1 < cnt;
+      uint32_t st[8];
+      if (threadIdx.x < 64) {
+        const uint32_t* Ld = src + (2 * i) * 8;
+        if (i < out_cnt && !pair)
+#pragma unroll
+          for (int t = 0; t < 8; t++) dst[i * 8 + t] = Ld[t];
+        uint32_t m[16];
+        sha256_init(st);
+        rfc_node_block<0>(Ld, src + (2 * i + 1) * 8, m);
+        sha256_compress(st, m);
+      } else if (threadIdx.x < 128) {
+        uint32_t m[16];
+        rfc_node_block<1>(src + (2 * i) * 8, src + (2 * i + 1) * 8, m);
+        sha256_kw_store(m, kw + i * kKwStride);
+      }
+      __syncthreads();
+      if (threadIdx.x < 64) {
+        sha256_rounds_kw(st, kw + i * kKwStride);
+        if (pair)
+#pragma unroll
+          for (int t = 0; t < 8; t++) dst[i * 8 + t] = st[t];
+      }
+    }
+    __syncthreads();
+    if (NODES) {
+      for (int i = threadIdx.x; i < out_cnt * 8; i += blockDim.x) nodes_out[base * 8 + i] = bswap(dst[i]);
+      base += out_cnt;
+    }
+    uint32_t* tmp = src;
+    src = dst;
+    dst = tmp;
+    cnt = out_cnt;
+  }
+  if (threadIdx.x < 8) out[threadIdx.x] = bswap(src[threadIdx.x]);
+}
+
 }  // namespace cda

@@ -189,6 +189,33 @@ int cda_multi_init_replicas(int device, uint32_t count, cda_multi** out);
 int cda_extend_commit_device(cda_ctx* ctx, uint32_t k, uint32_t nblocks, const void* d_ods, void* d_eds,
                              void* d_roots, void* d_dah, void* d_status, void* stream);
 
+/* ---- blocks of different sizes in one call (a node that replays or audits a range of heights) ----
+ * Block b is a ks[b] x ks[b] square of 512-byte shares.  ks is a host array in both forms and has been read when the
+ * call returns.  Every buffer is packed in block order with no padding; block b starts at
+ *   ods: sum_{i<b} k_i^2 * 512      eds: sum_{i<b} 4 k_i^2 * 512      row_roots / col_roots: sum_{i<b} 2 k_i * 90
+ *   dah: 32 b       d_roots: sum_{i<b} 4 k_i records of 96 B (a block's row roots, then its column roots, as
+ *   cda_extend_commit_device lays them out)       d_status: one uint64 per block, encoded as there.
+ * Block b comes out byte for byte as cda_extend_commit returns it for that block alone: EDS, roots and DAH.
+ * Blocks with k <= CDA_OPT_MIXED_SMALL_MAX go together, whatever their sizes, into one launch of a kernel that takes
+ * a square from ODS to DAH in a single workgroup.  The host form groups the other blocks by k and runs each group as
+ * cda_extend_commit_batch runs a batch on the context's stream (k = 256 and 512 on GF(2^16) included).  The device
+ * form gathers nothing: each maximal run of consecutive larger blocks of equal k is one pass of the
+ * cda_extend_commit_device pipeline over that sub-range, so a caller who wants its large blocks fully batched
+ * orders them by size.  The device form is asynchronous on `stream`, as cda_extend_commit_device is; the ODS must
+ * not overlap the EDS.
+ * Errors: CDA_E_ARG (a null argument, nblocks == 0); CDA_E_NOT_POW2 (some ks[b] is not a power of two; err->block =
+ * the lowest such b); CDA_E_UNSUPPORTED (some ks[b] > 512; err->block = the lowest such b); CDA_E_NS_ORDER (host
+ * form: err->block = the lowest failing block, axis / index / leaf what cda_extend_commit reports for that block
+ * alone).
+ * CDA_OPT_MIXED_SMALL_MAX (cda_set_option, per context): the largest k that goes to the one-workgroup kernel: 0
+ * (none), 1, 2, 4 or 8 (the default); any other value is CDA_E_ARG.  The results are the same bytes at every value. */
+int cda_extend_commit_mixed(cda_ctx* ctx, uint32_t nblocks, const uint32_t* ks, const uint8_t* ods,
+                            uint8_t* eds_or_null, uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
+                            cda_err_info* err);
+int cda_extend_commit_mixed_device(cda_ctx* ctx, uint32_t nblocks, const uint32_t* ks, const void* d_ods,
+                                   void* d_eds, void* d_roots, void* d_dah, void* d_status, void* stream);
+enum { CDA_OPT_MIXED_SMALL_MAX = 2 }; /* cda_set_option */
+
 /* ---- device-resident building blocks (one square split over GPUs) ----
  * All pointers are device memory of this ctx's GPU; asynchronous on `stream`
  * (hipStream_t or NULL).  They share the ctx's scratch workspace, so calls on
