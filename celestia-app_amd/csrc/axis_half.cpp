@@ -8,29 +8,62 @@
 //   cda_square_rebuild_axes           halves in host memory -> a retained square: stage, assemble into the handle's
 //                                     EDS area, rsmt2d Repair there, commit in place
 // The host checks arguments and copies; every check of a half is the kernels': axis_half_kernels.hip around the
-// decode, encode and axis-root launches the library already has, on one stream with no host wait between them.  The
-// repair is repair.cpp's and the commitment sampling.cpp's, both unchanged.
+// decode, encode and axis-root launches the library already has (complete_axes, which befp.cpp runs too), on one
+// stream with no host wait between them.  The repair and the commitment of a rebuild are rebuild.cpp's
+// rebuild_finish, shared with cda_square_rebuild.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <vector>
-
+#include "axis_half.h"
 #include "ctx.h"
-#include "sampling.h"
+#include "rebuild.h"
 
 using namespace cda;
 
-namespace {
+namespace cda {
 
-// k and nhalves of a call: a power of two the axis-root kernel takes whole (2k leaves in one workgroup's LDS)
-int check_shape(uint32_t k, uint32_t nhalves) {
-  if (!is_pow2(k)) return CDA_E_NOT_POW2;
+int check_axis_shape(uint32_t k, uint32_t n, int not_pow2) {
+  if (!is_pow2(k)) return not_pow2;
   if (2 * (uint64_t)k > (uint64_t)kAxisRootsMaxLeaves) return CDA_E_UNSUPPORTED;
-  if ((uint64_t)nhalves * 2 * k > 0x7FFFFFFFull) return CDA_E_UNSUPPORTED;  // slots are 32-bit, launches take int
+  if ((uint64_t)n * 2 * k > 0x7FFFFFFFull) return CDA_E_UNSUPPORTED;  // slots are 32-bit, launches take int
   return CDA_OK;
 }
 
-int code_of(int lr) { return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE; }
+int complete_axes(cda_ctx* c, const AxisBufs& b, uint32_t n, uint32_t k, bool decode, const AxisScopes& scopes,
+                  hipStream_t s) {
+  const uint32_t w = 2 * k;
+  int lr;
+  if (decode) {
+    ProfScope ps(c, scopes.decode, s);
+    if ((lr = launch_rs_decode(b.axes, b.cw_off, b.cw_stride, b.mask, (int)n, (int)k, CDA_SHARE, s)))
+      return code_of(lr);
+  }
+  {  // slots [k, 2k) of every buffer := Encode(slots [0, k)); of a decoded axis that is what was sent
+    RsJob j{};
+    j.src = b.axes;
+    j.src_cw = (long long)w * CDA_SHARE;
+    j.src_sh = CDA_SHARE;
+    j.dst = b.axes + (size_t)k * CDA_SHARE;
+    j.dst_cw = (long long)w * CDA_SHARE;
+    j.dst_sh = CDA_SHARE;
+    j.k = (int)k;
+    j.cw_per_blk = (int)n;
+    j.nblk = 1;
+    j.shard_len = CDA_SHARE;
+    const bool ff8 = w <= 256;
+    ProfScope ps(c, ff8 ? scopes.encode8 : scopes.encode16, s);
+    if ((lr = ff8 ? launch_rs_encode8(j, s) : launch_rs_encode16(j, s))) return code_of(lr);
+  }
+  {
+    ProfScope ps(c, scopes.roots, s);
+    if ((lr = launch_axis_roots(b.axes, (long long)w * CDA_SHARE, (int)w, k, b.axis_idx, (int)n, b.recs, b.status, s)))
+      return code_of(lr);
+  }
+  return CDA_OK;
+}
+
+}  // namespace cda
+
+namespace {
 
 // The arguments of a call as the caller gave them: host pointers in the host forms (where the outputs are bound
 // later), device pointers in the _device forms.
@@ -61,10 +94,9 @@ bool any_second_side(const cda_axis_half_desc* descs, uint32_t n) {
 }
 
 // H0-H2 once every pointer of `a` is device memory, the workspace is bound and a.axes points at nhalves x 2k x 512 B
-// (the caller has sized both): the six launches.  decode: some half may be a second side (a device form cannot know).
+// (the caller has sized both): the six launches.  decode: some half may be a second side (a device form cannot know);
+// slots [0, k) of the second sides' buffers := Decode(slots [k, 2k)).
 int verify_core(cda_ctx* c, const AxisHalfArgs& a, bool decode, hipStream_t s) {
-  const uint32_t k = a.k, w = 2 * k;
-  int lr;
   {
     ProfScope ps(c, "axis_half_prep", s);
     if (launch_axis_half_prep(a, s)) return CDA_E_DEVICE;
@@ -73,33 +105,12 @@ int verify_core(cda_ctx* c, const AxisHalfArgs& a, bool decode, hipStream_t s) {
     ProfScope ps(c, "axis_half_scatter", s);
     if (launch_axis_half_scatter(a, s)) return CDA_E_DEVICE;
   }
-  if (decode) {  // slots [0, k) of the second sides' buffers := Decode(slots [k, 2k))
-    ProfScope ps(c, "axis_half_rs_decode", s);
-    if ((lr = launch_rs_decode(a.axes, a.cw_off, a.cw_stride, a.mask, (int)a.nhalves, (int)k, CDA_SHARE, s)))
-      return code_of(lr);
-  }
-  {  // slots [k, 2k) of every buffer := Encode(slots [0, k)); of a decoded axis that is what was sent
-    RsJob j{};
-    j.src = a.axes;
-    j.src_cw = (long long)w * CDA_SHARE;
-    j.src_sh = CDA_SHARE;
-    j.dst = a.axes + (size_t)k * CDA_SHARE;
-    j.dst_cw = (long long)w * CDA_SHARE;
-    j.dst_sh = CDA_SHARE;
-    j.k = (int)k;
-    j.cw_per_blk = (int)a.nhalves;
-    j.nblk = 1;
-    j.shard_len = CDA_SHARE;
-    const bool ff8 = w <= 256;
-    ProfScope ps(c, ff8 ? "axis_half_rs_encode8" : "axis_half_rs_encode16", s);
-    if ((lr = ff8 ? launch_rs_encode8(j, s) : launch_rs_encode16(j, s))) return code_of(lr);
-  }
-  {
-    ProfScope ps(c, "axis_half_axis_roots", s);
-    if ((lr = launch_axis_roots(a.axes, (long long)w * CDA_SHARE, (int)w, k, a.axis_idx, (int)a.nhalves, a.recs,
-                                a.status, s)))
-      return code_of(lr);
-  }
+  if (int rc = complete_axes(c, AxisBufs{a.axes, a.cw_off, a.cw_stride, a.mask, a.axis_idx, a.recs, a.status},
+                             a.nhalves, a.k, decode,
+                             AxisScopes{"axis_half_rs_decode", "axis_half_rs_encode8", "axis_half_rs_encode16",
+                                        "axis_half_axis_roots"},
+                             s))
+    return rc;
   {
     ProfScope ps(c, "axis_half_combine", s);
     if (launch_axis_half_combine(a, s)) return CDA_E_DEVICE;
@@ -170,7 +181,7 @@ int cda_axis_halves_verify(cda_ctx* c, uint32_t k, uint32_t nhalves, const cda_a
                            const uint8_t* shares, const uint8_t* roots, uint32_t nroots, uint8_t* statuses,
                            uint8_t* axes_or_null) {
   CDA_API_TRY
-  if (int rc = check_shape(k, nhalves)) return rc;
+  if (int rc = check_axis_shape(k, nhalves, CDA_E_NOT_POW2)) return rc;
   if (!c) return CDA_E_ARG;
   const AxisHalfArgs h = half_args(k, nhalves, descs, shares, roots, nroots, statuses, false);
   if (missing(h)) return CDA_E_ARG;
@@ -204,7 +215,7 @@ int cda_axis_halves_verify_device(cda_ctx* c, uint32_t k, uint32_t nhalves, cons
                                   const void* d_shares, const void* d_roots, uint32_t nroots, void* d_statuses,
                                   void* d_axes_or_null, void* stream) {
   CDA_API_TRY
-  if (int rc = check_shape(k, nhalves)) return rc;
+  if (int rc = check_axis_shape(k, nhalves, CDA_E_NOT_POW2)) return rc;
   if (!c) return CDA_E_ARG;
   AxisHalfArgs a = half_args(k, nhalves, d_descs, d_shares, d_roots, nroots, d_statuses, false);
   if (missing(a)) return CDA_E_ARG;
@@ -230,7 +241,7 @@ int cda_axis_halves_assemble_device(cda_ctx* c, uint32_t k, uint32_t nhalves, co
                                     const void* d_shares, const void* d_roots, void* d_eds, void* d_present,
                                     void* d_statuses, void* stream) {
   CDA_API_TRY
-  if (int rc = check_shape(k, nhalves)) return rc;
+  if (int rc = check_axis_shape(k, nhalves, CDA_E_NOT_POW2)) return rc;
   if (!c) return CDA_E_ARG;
   AxisHalfArgs a = half_args(k, nhalves, d_descs, d_shares, d_roots, 4 * k, d_statuses, true);
   if (missing(a) || !d_eds || !d_present) return CDA_E_ARG;
@@ -258,17 +269,12 @@ int cda_square_rebuild_axes(cda_ctx* c, uint32_t k, uint32_t nhalves, const cda_
   CDA_API_TRY
   set_err(err, CDA_OK, -1, -1, -1, -1);
   if (out) *out = nullptr;
-  if (int rc = check_shape(k, nhalves)) return rc;
+  if (int rc = check_axis_shape(k, nhalves, CDA_E_NOT_POW2)) return rc;
   if (!c || !out || !row_roots || !col_roots || !dah) return CDA_E_ARG;
   const AxisHalfArgs h = half_args(k, nhalves, descs, shares, nullptr, 4 * k, statuses, true);
   if (nhalves && (!descs || !shares || !statuses)) return CDA_E_ARG;
-  const uint32_t w = 2 * k;
-  const size_t cells = cells_of(k), roots_b = (size_t)w * CDA_NODE_SIZE;
-  std::vector<uint8_t> roots(2 * roots_b);  // rows then columns, as the rule indexes them
-  memcpy(roots.data(), row_roots, roots_b);
-  memcpy(roots.data() + roots_b, col_roots, roots_b);
-  std::vector<uint8_t> own_present(present_or_null ? 0 : cells);
-  uint8_t* present = present_or_null ? present_or_null : own_present.data();
+  const size_t cells = cells_of(k);
+  RebuildHost host(k, row_roots, col_roots, present_or_null);
   Lock l(c);
   hipStream_t s = c->stream;
   int rc;
@@ -281,7 +287,7 @@ int cda_square_rebuild_axes(cda_ctx* c, uint32_t k, uint32_t nhalves, const cda_
   a.eds = b.eds;
   auto lay = [&](Stage& st) {
     a.descs = st.stage(h.descs, nhalves);
-    a.roots = st.stage(roots.data(), roots.size());
+    a.roots = st.stage(host.roots.data(), host.roots.size());
     a.statuses = st.ar.take<uint8_t>(nhalves);
     a.present = st.ar.take<uint8_t>(cells);
   };
@@ -296,26 +302,8 @@ int cda_square_rebuild_axes(cda_ctx* c, uint32_t k, uint32_t nhalves, const cda_
   a.axes = (uint8_t*)c->scratch.p;
   if (nhalves && (rc = staged_h2d(c, c->payload.p, shares, shares_bytes(a), s))) return rc;
   if ((rc = assemble_core(c, a, nhalves && any_second_side(descs, nhalves), s))) return rc;
-  // the presence map and the statuses back in one wait: the repair plans on the host
-  if (!dev_ok(c, hipMemcpyAsync(present, a.present, cells, hipMemcpyDeviceToHost, s), "D2H") ||
-      (nhalves && !dev_ok(c, hipMemcpyAsync(statuses, a.statuses, nhalves, hipMemcpyDeviceToHost, s), "D2H")) ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  const int repaired = repair_resident(c, k, b.eds, present, row_roots, col_roots, err, s);
-  if (repaired != CDA_OK && repaired != CDA_E_UNREPAIRABLE && repaired != CDA_E_BYZANTINE) return repaired;
-  // the square as far as rsmt2d got (cda_repair's return), or the repaired one
-  if (eds_or_null && (rc = staged_d2h(c, eds_or_null, b.eds, b.eds_b, s))) return rc;
-  if (repaired != CDA_OK) return repaired;  // `b` releases the handle's memory
-  std::vector<uint8_t> got(2 * roots_b);
-  if ((rc = square_commit(c, k, b, out, got.data(), got.data() + roots_b, dah, err, s))) return rc;
-  if (memcmp(got.data(), roots.data(), roots.size()) != 0) {  // an OK repair has checked every axis against its root
-    cda_square_close(*out);
-    *out = nullptr;
-    c->last_err = "cda_square_rebuild_axes: the repaired square does not commit to the given roots";
-    return CDA_E_INTERNAL;
-  }
-  return CDA_OK;
+  return rebuild_finish(c, k, b, a.present, a.statuses, nhalves, statuses, host, eds_or_null, out, dah, err,
+                        "cda_square_rebuild_axes", s);
   CDA_API_CATCH(c)
 }
 

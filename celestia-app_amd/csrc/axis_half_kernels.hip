@@ -19,9 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "axis_half.h"
 #include "axis_half_rule.h"
 #include "cda_internal.h"
-#include "sampling.h"
 
 namespace cda {
 

@@ -198,8 +198,6 @@ void copy_out(AxisReq* r, const uint8_t* h) {
   }
 }
 
-int code_of(int lr) { return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE; }
-
 // The batch on the device: one launch per group on the slot's stream, reading and writing the page-locked staging
 // itself (zero-copy: a batch's bytes cross the link once each way, with no DMA submissions), then one
 // synchronisation of that stream.  The context lock is held only while launching (profiling events, error text),

@@ -1,26 +1,17 @@
 // befp.cpp — C ABI of the bad-encoding fraud proofs (include/cda.h): batched Validate of proofs that an
 // axis of a committed square is not a Reed-Solomon codeword (specs fraud_proofs.md; rsmt2d ErrByzantineData is what
 // cda_repair reports as CDA_E_BYZANTINE).  The host checks arguments and copies; every check of a proof is the
-// kernels': befp_kernels.hip around the verify, decode, encode and axis-root launches the library already has, on one
-// stream with no host wait between them.
+// kernels': befp_kernels.hip around the verify launch and the completion of the axes (complete_axes, axis_half.h) the
+// library already has, on one stream with no host wait between them.
 #include <hip/hip_runtime.h>
 
+#include "axis_half.h"
+#include "befp.h"
 #include "ctx.h"
-#include "sampling.h"
 
 using namespace cda;
 
 namespace {
-
-// k of a call: a power of two the axis-root kernel takes whole (2k leaves in one workgroup's LDS)
-int check_k(uint32_t k, uint32_t nproofs) {
-  if (!is_pow2(k)) return CDA_E_ARG;
-  if (2 * (uint64_t)k > (uint64_t)kAxisRootsMaxLeaves) return CDA_E_UNSUPPORTED;
-  if ((uint64_t)nproofs * 2 * k > 0x7FFFFFFFull) return CDA_E_UNSUPPORTED;  // slots are 32-bit, launches take int
-  return CDA_OK;
-}
-
-int code_of(int lr) { return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE; }
 
 // The arguments of a call as the caller gave them: host pointers in the host form, device pointers in the _device form.
 BefpArgs befp_args(uint32_t k, uint32_t nproofs, const void* descs, const void* entries, uint32_t nentries,
@@ -42,8 +33,7 @@ size_t axes_bytes(const BefpArgs& a) { return (size_t)a.nproofs * 2 * a.k * CDA_
 int enqueue_befp(cda_ctx* c, BefpArgs& a, Arena ws, hipStream_t s) {
   befp_workspace(a, ws);
   a.axes = (uint8_t*)c->scratch.p;
-  const uint32_t k = a.k, w = 2 * k, slots = a.nproofs * w;
-  int lr;
+  const uint32_t slots = a.nproofs * 2 * a.k;
   {
     ProfScope ps(c, "befp_prep", s);
     if (launch_befp_prep(a, s)) return CDA_E_DEVICE;
@@ -58,33 +48,10 @@ int enqueue_befp(cda_ctx* c, BefpArgs& a, Arena ws, hipStream_t s) {
     ProfScope ps(c, "befp_gather", s);
     if (launch_befp_gather(a, s)) return CDA_E_DEVICE;
   }
-  {
-    ProfScope ps(c, "befp_rs_decode", s);
-    if ((lr = launch_rs_decode(a.axes, a.cw_off, a.cw_stride, a.mask, (int)a.nproofs, (int)k, CDA_SHARE, s)))
-      return code_of(lr);
-  }
-  {  // slots [k, 2k) of every buffer := Encode(slots [0, k))
-    RsJob j{};
-    j.src = a.axes;
-    j.src_cw = (long long)w * CDA_SHARE;
-    j.src_sh = CDA_SHARE;
-    j.dst = a.axes + (size_t)k * CDA_SHARE;
-    j.dst_cw = (long long)w * CDA_SHARE;
-    j.dst_sh = CDA_SHARE;
-    j.k = (int)k;
-    j.cw_per_blk = (int)a.nproofs;
-    j.nblk = 1;
-    j.shard_len = CDA_SHARE;
-    const bool ff8 = w <= 256;
-    ProfScope ps(c, ff8 ? "befp_rs_encode8" : "befp_rs_encode16", s);
-    if ((lr = ff8 ? launch_rs_encode8(j, s) : launch_rs_encode16(j, s))) return code_of(lr);
-  }
-  {
-    ProfScope ps(c, "befp_axis_roots", s);
-    if ((lr = launch_axis_roots(a.axes, (long long)w * CDA_SHARE, (int)w, k, a.axis_idx, (int)a.nproofs, a.recs,
-                                a.status, s)))
-      return code_of(lr);
-  }
+  if (int rc = complete_axes(c, AxisBufs{a.axes, a.cw_off, a.cw_stride, a.mask, a.axis_idx, a.recs, a.status},
+                             a.nproofs, a.k, true,
+                             AxisScopes{"befp_rs_decode", "befp_rs_encode8", "befp_rs_encode16", "befp_axis_roots"}, s))
+    return rc;
   {
     ProfScope ps(c, "befp_combine", s);
     if (launch_befp_combine(a, s)) return CDA_E_DEVICE;
@@ -101,7 +68,7 @@ int cda_befp_validate(cda_ctx* c, uint32_t k, uint32_t nproofs, const cda_befp_d
                       uint32_t nnodes_total, const uint8_t* roots, uint32_t nroots, int32_t* verdicts) {
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
-  if (int rc = check_k(k, nproofs)) return rc;
+  if (int rc = check_axis_shape(k, nproofs, CDA_E_ARG)) return rc;
   if (nproofs == 0) return CDA_OK;
   const BefpArgs h = befp_args(k, nproofs, descs, entries, nentries, shares, nodes, nnodes_total, roots, nroots,
                                verdicts);
@@ -138,7 +105,7 @@ int cda_befp_validate_device(cda_ctx* c, uint32_t k, uint32_t nproofs, const voi
                              const void* d_roots, uint32_t nroots, void* d_verdicts, void* stream) {
   CDA_API_TRY
   if (!c) return CDA_E_ARG;
-  if (int rc = check_k(k, nproofs)) return rc;
+  if (int rc = check_axis_shape(k, nproofs, CDA_E_ARG)) return rc;
   if (nproofs == 0) return CDA_OK;
   BefpArgs a = befp_args(k, nproofs, d_descs, d_entries, nentries, d_shares, d_nodes, nnodes_total, d_roots, nroots,
                          d_verdicts);

@@ -8,9 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "befp.h"
 #include "befp_rule.h"
 #include "cda_internal.h"
-#include "sampling.h"
 
 namespace cda {
 

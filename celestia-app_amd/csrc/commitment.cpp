@@ -7,14 +7,14 @@
 //                                        pkg/inclusion/get_commit.go) hashed on the device in the same call
 //   cda_commitment_proofs_verify[_device]  rules C0-C8 of a batch
 // The host checks arguments against commitment_rule.h, sizes and copies; which nodes make a proof and every hash are
-// sampling_kernels.hip's.  Staging, the two forms of the verifier and the workspace as in sampling.cpp.
+// commitment_kernels.hip's.  Staging, the two forms of the verifier and the workspace as in sampling.cpp.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
+#include "commitment.h"
 #include "commitment_rule.h"
 #include "ctx.h"
-#include "sampling.h"
 
 using namespace cda;
 

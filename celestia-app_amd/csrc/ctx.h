@@ -174,6 +174,8 @@ inline int verdicts_back(cda_ctx* c, void* dst, const void* d_src, size_t n, hip
   flush_profile(c);
   return CDA_OK;
 }
+// a launcher's non-zero result as a return code: -2 says the launcher does not take the shape
+inline int code_of(int lr) { return lr == -2 ? CDA_E_UNSUPPORTED : CDA_E_DEVICE; }
 int ilog2i(uint32_t v);
 bool is_pow2(uint64_t v);
 void set_err(cda_err_info* e, int code, int axis, int index, int leaf, int block);

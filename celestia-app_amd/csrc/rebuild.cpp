@@ -15,9 +15,51 @@
 #include <vector>
 
 #include "ctx.h"
-#include "sampling.h"
+#include "rebuild.h"
 
 using namespace cda;
+
+namespace cda {
+
+// ---- the head and the tail of a rebuild (rebuild.h): what cda_square_rebuild and cda_square_rebuild_axes share ----
+RebuildHost::RebuildHost(uint32_t k, const uint8_t* rr, const uint8_t* cr, uint8_t* present_or_null)
+    : row_roots(rr), col_roots(cr), roots(4 * (size_t)k * CDA_NODE_SIZE),
+      own_present(present_or_null ? 0 : 4 * (size_t)k * k),
+      present(present_or_null ? present_or_null : own_present.data()) {
+  const size_t roots_b = 2 * (size_t)k * CDA_NODE_SIZE;
+  memcpy(roots.data(), rr, roots_b);
+  memcpy(roots.data() + roots_b, cr, roots_b);
+}
+
+int rebuild_finish(cda_ctx* c, uint32_t k, SquareBuild& b, const uint8_t* d_present, const uint8_t* d_statuses,
+                   uint32_t n, uint8_t* statuses, RebuildHost& h, uint8_t* eds_or_null, cda_square** out, uint8_t* dah,
+                   cda_err_info* err, const char* call, hipStream_t s) {
+  const size_t cells = 4 * (size_t)k * k, roots_b = h.roots.size() / 2;
+  int rc;
+  // the presence map and the statuses back in one wait: the repair plans on the host
+  if (!dev_ok(c, hipMemcpyAsync(h.present, d_present, cells, hipMemcpyDeviceToHost, s), "D2H") ||
+      (n && !dev_ok(c, hipMemcpyAsync(statuses, d_statuses, n, hipMemcpyDeviceToHost, s), "D2H")) ||
+      !dev_ok(c, hipStreamSynchronize(s), "sync"))
+    return CDA_E_DEVICE;
+  flush_profile(c);
+  const int repaired = repair_resident(c, k, b.eds, h.present, h.row_roots, h.col_roots, err, s);
+  if (repaired != CDA_OK && repaired != CDA_E_UNREPAIRABLE && repaired != CDA_E_BYZANTINE) return repaired;
+  // the square as far as rsmt2d got (cda_repair's return), or the repaired one
+  if (eds_or_null && (rc = staged_d2h(c, eds_or_null, b.eds, b.eds_b, s))) return rc;
+  if (repaired != CDA_OK) return repaired;  // `b` releases the handle's memory
+  std::vector<uint8_t> got(2 * roots_b);
+  if ((rc = square_commit(c, k, b, out, got.data(), got.data() + roots_b, dah, err, s))) return rc;
+  // an OK repair has checked every axis against its root
+  if (memcmp(got.data(), h.roots.data(), h.roots.size()) != 0) {
+    cda_square_close(*out);
+    *out = nullptr;
+    c->last_err = std::string(call) + ": the repaired square does not commit to the given roots";
+    return CDA_E_INTERNAL;
+  }
+  return CDA_OK;
+}
+
+}  // namespace cda
 
 namespace {
 
@@ -128,13 +170,8 @@ int cda_square_rebuild(cda_ctx* c, uint32_t k, uint32_t nsamples, const cda_samp
                                        statuses);
   if (missing(h)) return CDA_E_ARG;
   if (int rc = check_shape(k, nsamples)) return rc;
-  const uint32_t w = 2 * k;
-  const size_t cells = cells_of(k), roots_b = (size_t)w * CDA_NODE_SIZE;
-  std::vector<uint8_t> roots(2 * roots_b);  // rows then columns, as the verifier indexes them
-  memcpy(roots.data(), row_roots, roots_b);
-  memcpy(roots.data() + roots_b, col_roots, roots_b);
-  std::vector<uint8_t> own_present(present_or_null ? 0 : cells);
-  uint8_t* present = present_or_null ? present_or_null : own_present.data();
+  const size_t cells = cells_of(k);
+  RebuildHost host(k, row_roots, col_roots, present_or_null);
   Lock l(c);
   hipStream_t s = c->stream;
   int rc;
@@ -148,7 +185,7 @@ int cda_square_rebuild(cda_ctx* c, uint32_t k, uint32_t nsamples, const cda_samp
   a.eds = b.eds;
   auto lay = [&](Stage& st) {
     a.descs = st.stage(h.descs, nsamples);
-    a.roots = st.stage(roots.data(), roots.size());
+    a.roots = st.stage(host.roots.data(), host.roots.size());
     a.statuses = st.ar.take<uint8_t>(nsamples);
     a.present = st.ar.take<uint8_t>(cells);
   };
@@ -163,26 +200,8 @@ int cda_square_rebuild(cda_ctx* c, uint32_t k, uint32_t nsamples, const cda_samp
   if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
   if (shares_b && (rc = staged_h2d(c, c->payload.p, shares, shares_b, s))) return rc;
   if ((rc = assemble_core(c, a, st.ar, s))) return rc;
-  // the presence map and the statuses back in one wait: the repair plans on the host
-  if (!dev_ok(c, hipMemcpyAsync(present, a.present, cells, hipMemcpyDeviceToHost, s), "D2H") ||
-      (nsamples && !dev_ok(c, hipMemcpyAsync(statuses, a.statuses, nsamples, hipMemcpyDeviceToHost, s), "D2H")) ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  const int repaired = repair_resident(c, k, b.eds, present, row_roots, col_roots, err, s);
-  if (repaired != CDA_OK && repaired != CDA_E_UNREPAIRABLE && repaired != CDA_E_BYZANTINE) return repaired;
-  // the square as far as rsmt2d got (cda_repair's return), or the repaired one
-  if (eds_or_null && (rc = staged_d2h(c, eds_or_null, b.eds, b.eds_b, s))) return rc;
-  if (repaired != CDA_OK) return repaired;  // `b` releases the handle's memory
-  std::vector<uint8_t> got(2 * roots_b);
-  if ((rc = square_commit(c, k, b, out, got.data(), got.data() + roots_b, dah, err, s))) return rc;
-  if (memcmp(got.data(), roots.data(), roots.size()) != 0) {  // an OK repair has checked every axis against its root
-    cda_square_close(*out);
-    *out = nullptr;
-    c->last_err = "cda_square_rebuild: the repaired square does not commit to the given roots";
-    return CDA_E_INTERNAL;
-  }
-  return CDA_OK;
+  return rebuild_finish(c, k, b, a.present, a.statuses, nsamples, statuses, host, eds_or_null, out, dah, err,
+                        "cda_square_rebuild", s);
   CDA_API_CATCH(c)
 }
 

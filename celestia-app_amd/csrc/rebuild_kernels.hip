@@ -12,8 +12,8 @@
 #include <stdint.h>
 
 #include "cda_internal.h"
+#include "rebuild.h"
 #include "sample_place_rule.h"
-#include "sampling.h"
 
 namespace cda {
 

@@ -8,19 +8,14 @@
 //                              any row or column tree, many ranges per launch
 //   cda_nmt_verify[_device]    nmt Proof.VerifyInclusion as ShareProof.VerifyProof calls it
 //                              (pkg/proof/share_proof.go:53-82), many proofs per launch
-//   cda_square_share_proofs    pkg/proof NewShareInclusionProof (proof.go:55-167) for many share ranges per launch:
-//                              NMT range proofs, row roots and their RFC-6962 proofs in the data root
-//   cda_share_proofs_validate[_device]  ShareProof.Validate (share_proof.go:16-82, row_proof.go:13-48) of a batch
-//   cda_square_prove_namespace nmt ProveNamespace of any row or column tree: the namespace's shares with an inclusion
-//                              proof, or an absence or an empty proof, many queries per launch
-//   cda_nmt_verify_namespace[_device]   nmt Proof.VerifyNamespace (completeness included) of a batch
-// The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.
+// The host checks arguments and copies; which nodes make a proof and every hash are sampling_kernels.hip's.  The share
+// proofs and the namespace proofs of a retained square are share_proof.cpp and namespace_proof.cpp.
 //
-// Staging: a call's small arrays go into slots of c->plan that one function of a Stage (ctx.h) states; it runs on a
-// measuring arena to size the buffer, then on the buffer to copy.  Nodes and shares go through staged_h2d into
-// c->nodes and c->payload.  A verifier's host form stages its arrays and then runs what its _device form runs (the
-// *_core functions), with the kernels' workspace after its last slot.  Every ensure of a call comes before its first
-// copy: ensure may move a buffer.
+// Staging (here and in the other proof files): a call's small arrays go into slots of c->plan that one function of a
+// Stage (ctx.h) states; it runs on a measuring arena to size the buffer, then on the buffer to copy.  Nodes and shares
+// go through staged_h2d into c->nodes and c->payload.  A verifier's host form stages its arrays and then runs what its
+// _device form runs (the *_core functions), with the kernels' workspace after its last slot.  Every ensure of a call
+// comes before its first copy: ensure may move a buffer.
 //
 // Building a square is two steps, square_alloc and square_commit (sampling.h), with the EDS put in place between them:
 // by an upload or the extension here, by a device copy or by the assembly and repair of samples in rebuild.cpp.
@@ -163,9 +158,9 @@ int open_square(cda_ctx* c, uint32_t k, const uint8_t* src, bool extended, cda_s
   return square_commit(c, k, b, out, row_roots, col_roots, dah, err, s);
 }
 
-// ---- the three verifiers.  Per verifier: the arguments of a call as the caller gave them (host pointers in the host
-// form, device pointers in the _device form; the struct's own order), the sections a call may not leave out, and what
-// both forms end in once every pointer is device memory: the workspace bound at `ws`, the launches. ----
+// ---- the verifier (as every verifier's file has them): the arguments of a call as the caller gave them (host pointers
+// in the host form, device pointers in the _device form; the struct's own order), the sections a call may not leave
+// out, and what both forms end in once every pointer is device memory: the launches. ----
 VerifyArgs verify_args(const void* descs, const void* namespaces, const void* roots, const void* nodes,
                        const void* leaves, void* ok, uint32_t nproofs, uint32_t nroots, uint32_t nnodes_total,
                        uint32_t nleaves_total) {
@@ -180,42 +175,6 @@ bool missing(const VerifyArgs& a) {
 int nmt_verify_core(cda_ctx* c, const VerifyArgs& a, bool ranges, hipStream_t s) {
   ProfScope ps(c, "nmt_verify", s);
   return launch_nmt_verify(a, ranges, s) ? CDA_E_DEVICE : CDA_OK;
-}
-
-ValidateArgs validate_args(const void* descs, const void* rows, const void* row_roots, const void* leaf_hashes,
-                           const void* nodes, const void* aunts, const void* leaves, const void* data_roots,
-                           void* verdicts, uint32_t nproofs, uint32_t nrows, uint32_t nnodes, uint32_t naunts,
-                           uint32_t nleaves, uint32_t nroots) {
-  return ValidateArgs{(const cda_share_proof_desc*)descs, (const cda_share_row*)rows, (const uint8_t*)row_roots,
-                      (const uint8_t*)leaf_hashes, (const uint8_t*)nodes, (const uint8_t*)aunts,
-                      (const uint8_t*)leaves, (const uint8_t*)data_roots, (int32_t*)verdicts, nproofs, nrows, nnodes,
-                      naunts, nleaves, nroots};
-}
-bool missing(const ValidateArgs& a) {
-  return !a.descs || !a.verdicts || (a.nrows && (!a.rows || !a.row_roots || !a.leaf_hashes)) ||
-         (a.nnodes && !a.nodes) || (a.naunts && !a.aunts) || (a.nleaves && !a.leaves) || (a.nroots && !a.data_roots);
-}
-int share_validate_core(cda_ctx* c, ValidateArgs& a, Arena ws, hipStream_t s) {
-  validate_workspace(a, ws);
-  ProfScope ps(c, "share_proofs_validate", s);
-  return launch_share_proofs_validate(a, s) ? CDA_E_DEVICE : CDA_OK;
-}
-
-NsVerifyArgs ns_verify_args(const void* descs, const void* namespaces, const void* roots, const void* nodes,
-                            const void* leaf_hashes, const void* leaves, void* ok, uint32_t nproofs, uint32_t nroots,
-                            uint32_t nnodes_total, uint32_t nleaf_hashes, uint32_t nleaves_total) {
-  return NsVerifyArgs{(const cda_nmt_ns_proof_desc*)descs, (const uint8_t*)namespaces, (const uint8_t*)roots,
-                      (const uint8_t*)nodes, (const uint8_t*)leaf_hashes, (const uint8_t*)leaves, (uint8_t*)ok,
-                      nproofs, nroots, nnodes_total, nleaf_hashes, nleaves_total};
-}
-bool missing(const NsVerifyArgs& a) {
-  return !a.descs || !a.namespaces || !a.ok || (a.nroots && !a.roots) || (a.nnodes_total && !a.nodes) ||
-         (a.nleaf_hashes && !a.leaf_hashes) || (a.nleaves_total && !a.leaves);
-}
-int ns_verify_core(cda_ctx* c, NsVerifyArgs& a, Arena ws, hipStream_t s) {
-  ns_verify_workspace(a, ws);
-  ProfScope ps(c, "nmt_verify_namespace", s);
-  return launch_nmt_verify_namespace(a, s) ? CDA_E_DEVICE : CDA_OK;
 }
 
 }  // namespace
@@ -368,263 +327,6 @@ int cda_nmt_verify_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, con
   DevLock dl(c, (hipStream_t)stream);
   // the descriptors are device memory: whether any proof has more than one leaf is not known here
   return nmt_verify_core(c, a, true, dl.s);
-  CDA_API_CATCH(c)
-}
-
-int cda_square_share_proofs(cda_square* sq, uint32_t nq, const cda_share_range* q, uint32_t max_nodes,
-                            uint32_t rows_cap, uint32_t* row_off, cda_share_row* rows, uint8_t* nodes,
-                            uint8_t* row_roots, uint8_t* leaf_hashes, uint8_t* aunts, uint8_t* shares_or_null,
-                            uint64_t shares_cap, uint8_t* data_root) {
-  cda_ctx* c = sq ? sq->c : nullptr;
-  CDA_API_TRY
-  if (!c) return CDA_E_ARG;  // null, or a square whose context was freed
-  if (nq == 0) return CDA_OK;
-  if (!q || !row_off || !rows || !nodes || !row_roots || !leaf_hashes || !aunts || !data_root) return CDA_E_ARG;
-  if (nq > (1u << 24)) return CDA_E_UNSUPPORTED;
-  const uint32_t k = sq->k, naunts = (uint32_t)sq->view.log2w + 1;
-  if (max_nodes < 2 * (uint32_t)sq->view.log2w) return CDA_E_ARG;
-  // the queries against the square, and the sizes of the outputs: where each query's row records and shares start
-  std::vector<uint32_t> off(2 * (size_t)nq + 1);  // row_off (nq + 1) | share_off (nq)
-  uint64_t nrows = 0, nshares = 0;
-  for (uint32_t i = 0; i < nq; i++) {
-    if (q[i].start >= q[i].end || q[i].end > k * k) return CDA_E_ARG;
-    if (nrows > 0xFFFFFFFFull || nshares > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;
-    off[i] = (uint32_t)nrows;
-    off[nq + 1 + i] = (uint32_t)nshares;
-    nrows += (q[i].end - 1) / k - q[i].start / k + 1;
-    nshares += q[i].end - q[i].start;
-  }
-  if (nrows > rows_cap || (shares_or_null && nshares * CDA_SHARE > shares_cap)) return CDA_E_ARG;
-  if ((nrows * max_nodes) >> 32 || (nrows * naunts) >> 32 || nshares > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;
-  off[nq] = (uint32_t)nrows;
-  Lock l(c);
-  hipStream_t s = c->stream;
-  // staging in the context's workspace: queries | offsets | row records | row roots | leaf hashes | aunts, the nodes,
-  // the shares
-  const size_t aunts_b = nrows * naunts * 32;
-  const size_t nodes_b = nrows * max_nodes * CDA_NODE_SIZE, shares_b = shares_or_null ? nshares * CDA_SHARE : 0;
-  const cda_share_range* d_q = nullptr;
-  const uint32_t* d_off = nullptr;
-  ShareProofsOut o{};
-  auto lay = [&](Stage& st) {
-    d_q = st.stage(q, nq);
-    d_off = st.stage(off.data(), off.size());
-    o.rows = st.ar.take<cda_share_row>(nrows);
-    o.row_roots = st.ar.take<uint8_t>(nrows * CDA_NODE_SIZE);
-    o.leaf_hashes = st.ar.take<uint8_t>(nrows * 32);
-    o.aunts = st.ar.take<uint8_t>(aunts_b);
-  };
-  int rc;
-  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b)) ||
-      (shares_b && (rc = ensure(c, c->payload, shares_b))))
-    return rc;
-  Stage st{c, s, Arena(c->plan.p)};
-  lay(st);
-  if (!st.ok) return CDA_E_DEVICE;
-  o.nodes = (uint8_t*)c->nodes.p;
-  o.shares = shares_b ? (uint8_t*)c->payload.p : nullptr;
-  {
-    ProfScope ps(c, "square_share_proofs", s);
-    if (launch_square_share_proofs(sq->view, d_q, nq, d_off, d_off + nq + 1, (uint32_t)nrows, max_nodes, o, s))
-      return CDA_E_DEVICE;
-  }
-  const uint8_t* d_root = sq->view.dah_nodes + (2 * (size_t)(4 * k) - 2) * 32;  // the last node of the tree
-  if (!copy_any(c, row_off, d_off, ((size_t)nq + 1) * 4, s) ||
-      !copy_any(c, rows, o.rows, nrows * sizeof(cda_share_row), s) || !copy_any(c, nodes, o.nodes, nodes_b, s) ||
-      !copy_any(c, row_roots, o.row_roots, nrows * CDA_NODE_SIZE, s) ||
-      !copy_any(c, leaf_hashes, o.leaf_hashes, nrows * 32, s) || !copy_any(c, aunts, o.aunts, aunts_b, s) ||
-      !copy_any(c, shares_or_null, o.shares, shares_b, s) || !copy_any(c, data_root, d_root, 32, s) ||
-      !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  flush_profile(c);
-  return CDA_OK;
-  CDA_API_CATCH(c)
-}
-
-int cda_share_proofs_validate(cda_ctx* c, uint32_t nproofs, const cda_share_proof_desc* descs,
-                              const cda_share_row* rows, const uint8_t* row_roots, const uint8_t* leaf_hashes,
-                              uint32_t nrows, const uint8_t* nodes, uint32_t nnodes, const uint8_t* aunts,
-                              uint32_t naunts, const uint8_t* leaves, uint32_t nleaves, const uint8_t* data_roots,
-                              uint32_t nroots, int32_t* verdicts) {
-  CDA_API_TRY
-  if (!c) return CDA_E_ARG;
-  if (nproofs == 0) return CDA_OK;
-  const ValidateArgs h = validate_args(descs, rows, row_roots, leaf_hashes, nodes, aunts, leaves, data_roots, verdicts,
-                                       nproofs, nrows, nnodes, naunts, nleaves, nroots);
-  if (missing(h)) return CDA_E_ARG;
-  Lock l(c);
-  hipStream_t s = c->stream;
-  const size_t nodes_b = (size_t)nnodes * CDA_NODE_SIZE, leaves_b = (size_t)nleaves * CDA_SHARE;
-  ValidateArgs a = h;  // the same call on the staged copies; the kernels' workspace follows the verdicts
-  auto lay = [&](Stage& st) {
-    a.descs = st.stage(h.descs, nproofs);
-    a.rows = st.stage(h.rows, nrows);
-    a.row_roots = st.stage(h.row_roots, (size_t)nrows * CDA_NODE_SIZE);
-    a.leaf_hashes = st.stage(h.leaf_hashes, (size_t)nrows * 32);
-    a.aunts = st.stage(h.aunts, (size_t)naunts * 32);
-    a.data_roots = st.stage(h.data_roots, (size_t)nroots * 32);
-    a.verdicts = st.ar.take<int32_t>(nproofs);
-  };
-  int rc;
-  if ((rc = ensure(c, c->plan, staged_bytes(lay) + workspace_bytes(a, validate_workspace))) ||
-      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
-    return rc;
-  Stage st{c, s, Arena(c->plan.p)};
-  lay(st);
-  if (!st.ok) return CDA_E_DEVICE;
-  a.nodes = (const uint8_t*)c->nodes.p;
-  a.leaves = (const uint8_t*)c->payload.p;
-  if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
-  if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
-  if ((rc = share_validate_core(c, a, st.ar, s))) return rc;
-  return verdicts_back(c, verdicts, a.verdicts, (size_t)nproofs * 4, s);
-  CDA_API_CATCH(c)
-}
-
-int cda_share_proofs_validate_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, const void* d_rows,
-                                     const void* d_row_roots, const void* d_leaf_hashes, uint32_t nrows,
-                                     const void* d_nodes, uint32_t nnodes, const void* d_aunts, uint32_t naunts,
-                                     const void* d_leaves, uint32_t nleaves, const void* d_data_roots,
-                                     uint32_t nroots, void* d_verdicts, void* stream) {
-  CDA_API_TRY
-  if (!c) return CDA_E_ARG;
-  if (nproofs == 0) return CDA_OK;
-  ValidateArgs a = validate_args(d_descs, d_rows, d_row_roots, d_leaf_hashes, d_nodes, d_aunts, d_leaves, d_data_roots,
-                                 d_verdicts, nproofs, nrows, nnodes, naunts, nleaves, nroots);
-  if (missing(a)) return CDA_E_ARG;
-  // shares are read 16 bytes at a time, row records hold 64-bit fields, everything else is read in 4-byte words
-  if (((uintptr_t)d_leaves & 15) || ((uintptr_t)d_rows & 7) ||
-      (((uintptr_t)d_descs | (uintptr_t)d_row_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_nodes |
-        (uintptr_t)d_aunts | (uintptr_t)d_data_roots | (uintptr_t)d_verdicts) & 3))
-    return CDA_E_ARG;
-  DevLock dl(c, (hipStream_t)stream);
-  if (int rc = ensure(c, c->plan, workspace_bytes(a, validate_workspace))) return rc;
-  return share_validate_core(c, a, Arena(c->plan.p), dl.s);
-  CDA_API_CATCH(c)
-}
-
-int cda_square_prove_namespace(cda_square* sq, uint32_t nq, const cda_namespace_query* q, uint32_t max_nodes,
-                               cda_namespace_result* results, uint8_t* nodes, uint8_t* leaf_hashes,
-                               uint8_t* shares_or_null, uint64_t shares_cap, uint64_t* nshares_total) {
-  cda_ctx* c = sq ? sq->c : nullptr;
-  CDA_API_TRY
-  if (nshares_total) *nshares_total = 0;
-  if (!c || !nshares_total) return CDA_E_ARG;  // null, or a square whose context was freed
-  if (nq == 0) return CDA_OK;
-  if (!q || !results || !nodes || !leaf_hashes) return CDA_E_ARG;
-  if (nq > (1u << 24)) return CDA_E_UNSUPPORTED;
-  const uint32_t w = 2 * sq->k;
-  if (max_nodes < 2 * (uint32_t)sq->view.log2w) return CDA_E_ARG;
-  for (uint32_t i = 0; i < nq; i++)
-    if (q[i].axis > 1 || q[i].index >= w) return CDA_E_ARG;
-  if ((uint64_t)nq * w > 0xFFFFFFFFull) return CDA_E_UNSUPPORTED;  // share offsets are 32-bit
-  Lock l(c);
-  hipStream_t s = c->stream;
-  // staging in the context's workspace: queries | results | leaf hashes | the share total, the nodes, the shares
-  const size_t nodes_b = (size_t)nq * max_nodes * CDA_NODE_SIZE;
-  const cda_namespace_query* d_q = nullptr;
-  cda_namespace_result* d_res = nullptr;
-  uint8_t* d_lh = nullptr;
-  unsigned long long* d_total = nullptr;
-  auto lay = [&](Stage& st) {
-    d_q = st.stage(q, nq);
-    d_res = st.ar.take<cda_namespace_result>(nq);
-    d_lh = st.ar.take<uint8_t>((size_t)nq * CDA_NODE_SIZE);
-    d_total = st.ar.take<unsigned long long>(1);
-  };
-  int rc;
-  if ((rc = ensure(c, c->plan, staged_bytes(lay))) || (rc = ensure(c, c->nodes, nodes_b))) return rc;
-  Stage st{c, s, Arena(c->plan.p)};
-  lay(st);
-  if (!st.ok) return CDA_E_DEVICE;
-  {
-    ProfScope ps(c, "square_prove_namespace", s);
-    if (launch_square_prove_namespace(sq->view, d_q, nq, max_nodes, d_res, (uint8_t*)c->nodes.p, d_lh, d_total, s))
-      return CDA_E_DEVICE;
-  }
-  // How many shares the namespaces hold is the data's to say: with the shares wanted the host waits here, once, for
-  // the total that sizes their staging; without them the total comes back with everything else.
-  unsigned long long total = 0;
-  if (!dev_ok(c, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s), "D2H")) return CDA_E_DEVICE;
-  bool fits = true;
-  size_t shares_b = 0;
-  if (shares_or_null) {
-    if (!dev_ok(c, hipStreamSynchronize(s), "sync")) return CDA_E_DEVICE;
-    *nshares_total = total;
-    fits = total * CDA_SHARE <= shares_cap;
-    shares_b = fits ? (size_t)total * CDA_SHARE : 0;
-    if (shares_b) {
-      if ((rc = ensure(c, c->payload, shares_b))) return rc;
-      ProfScope ps(c, "namespace_shares", s);
-      if (launch_namespace_shares(sq->view, d_q, nq, d_res, (uint8_t*)c->payload.p, s)) return CDA_E_DEVICE;
-    }
-  }
-  if (!copy_any(c, results, d_res, (size_t)nq * sizeof(cda_namespace_result), s) ||
-      !copy_any(c, nodes, c->nodes.p, nodes_b, s) || !copy_any(c, leaf_hashes, d_lh, (size_t)nq * CDA_NODE_SIZE, s) ||
-      !copy_any(c, shares_or_null, c->payload.p, shares_b, s) || !dev_ok(c, hipStreamSynchronize(s), "sync"))
-    return CDA_E_DEVICE;
-  *nshares_total = total;
-  flush_profile(c);
-  return fits ? CDA_OK : CDA_E_ARG;
-  CDA_API_CATCH(c)
-}
-
-int cda_nmt_verify_namespace(cda_ctx* c, uint32_t nproofs, const cda_nmt_ns_proof_desc* descs,
-                             const uint8_t* namespaces, const uint8_t* roots, uint32_t nroots, const uint8_t* nodes,
-                             uint32_t nnodes_total, const uint8_t* leaf_hashes, uint32_t nleaf_hashes,
-                             const uint8_t* leaves, uint32_t nleaves_total, uint8_t* ok) {
-  CDA_API_TRY
-  if (!c) return CDA_E_ARG;
-  if (nproofs == 0) return CDA_OK;
-  const NsVerifyArgs h = ns_verify_args(descs, namespaces, roots, nodes, leaf_hashes, leaves, ok, nproofs, nroots,
-                                        nnodes_total, nleaf_hashes, nleaves_total);
-  if (missing(h)) return CDA_E_ARG;
-  for (uint32_t i = 0; i < nproofs; i++)
-    if (descs[i].end > kVerifyMaxEnd) return CDA_E_ARG;
-  Lock l(c);
-  hipStream_t s = c->stream;
-  const size_t nodes_b = (size_t)nnodes_total * CDA_NODE_SIZE, leaves_b = (size_t)nleaves_total * CDA_SHARE;
-  NsVerifyArgs a = h;  // the same call on the staged copies; the kernels' workspace follows the leaf hashes
-  auto lay = [&](Stage& st) {
-    a.descs = st.stage(h.descs, nproofs);
-    a.namespaces = st.stage(h.namespaces, (size_t)nproofs * CDA_NAMESPACE_SIZE);
-    a.ok = st.ar.take<uint8_t>(nproofs);
-    a.roots = st.stage(h.roots, (size_t)nroots * CDA_NODE_SIZE);
-    a.leaf_hashes = st.stage(h.leaf_hashes, (size_t)nleaf_hashes * CDA_NODE_SIZE);
-  };
-  int rc;
-  if ((rc = ensure(c, c->plan, staged_bytes(lay) + workspace_bytes(a, ns_verify_workspace))) ||
-      (rc = ensure(c, c->nodes, nodes_b)) || (rc = ensure(c, c->payload, leaves_b)))
-    return rc;
-  Stage st{c, s, Arena(c->plan.p)};
-  lay(st);
-  if (!st.ok) return CDA_E_DEVICE;
-  a.nodes = (const uint8_t*)c->nodes.p;
-  a.leaves = (const uint8_t*)c->payload.p;
-  if (nodes_b && (rc = staged_h2d(c, c->nodes.p, nodes, nodes_b, s))) return rc;
-  if (leaves_b && (rc = staged_h2d(c, c->payload.p, leaves, leaves_b, s))) return rc;
-  if ((rc = ns_verify_core(c, a, st.ar, s))) return rc;
-  return verdicts_back(c, ok, a.ok, nproofs, s);
-  CDA_API_CATCH(c)
-}
-
-int cda_nmt_verify_namespace_device(cda_ctx* c, uint32_t nproofs, const void* d_descs, const void* d_namespaces,
-                                    const void* d_roots, uint32_t nroots, const void* d_nodes, uint32_t nnodes_total,
-                                    const void* d_leaf_hashes, uint32_t nleaf_hashes, const void* d_leaves,
-                                    uint32_t nleaves_total, void* d_ok, void* stream) {
-  CDA_API_TRY
-  if (!c) return CDA_E_ARG;
-  if (nproofs == 0) return CDA_OK;
-  NsVerifyArgs a = ns_verify_args(d_descs, d_namespaces, d_roots, d_nodes, d_leaf_hashes, d_leaves, d_ok, nproofs,
-                                  nroots, nnodes_total, nleaf_hashes, nleaves_total);
-  if (missing(a)) return CDA_E_ARG;
-  // the kernels read shares 16 bytes and nodes, roots, leaf hashes and descriptors 4 bytes at a time
-  if (((uintptr_t)d_leaves & 15) ||
-      (((uintptr_t)d_nodes | (uintptr_t)d_roots | (uintptr_t)d_leaf_hashes | (uintptr_t)d_descs) & 3))
-    return CDA_E_ARG;
-  DevLock dl(c, (hipStream_t)stream);
-  if (int rc = ensure(c, c->plan, workspace_bytes(a, ns_verify_workspace))) return rc;
-  return ns_verify_core(c, a, Arena(c->plan.p), dl.s);
   CDA_API_CATCH(c)
 }
 

@@ -1,8 +1,9 @@
 // arena_check.cpp — CPU check of the carve helper (celestia-app_amd/csrc/arena.h) and of the three workspace layouts
-// that walk it (sampling.h: validate_workspace, ns_verify_workspace, befp_workspace), built and run under
-// AddressSanitizer + UndefinedBehaviorSanitizer by tests/test_sanitize.py.  No device is touched: each layout is
-// measured, then bound to a heap buffer of exactly the measured size, and every byte of every slot is written through
-// the bound pointers, so a slot the measuring walk did not count is a heap overflow the sanitizer reports.
+// that walk it (share_proof.h: validate_workspace, namespace_proof.h: ns_verify_workspace, befp.h: befp_workspace),
+// built and run under AddressSanitizer + UndefinedBehaviorSanitizer by tests/test_sanitize.py.  No device is touched:
+// each layout is measured, then bound to a heap buffer of exactly the measured size, and every byte of every slot is
+// written through the bound pointers, so a slot the measuring walk did not count is a heap overflow the sanitizer
+// reports.
 //
 // Per layout and shape: the first slot is the base (launch_share_proofs_validate clears the layout from its first
 // slot), every slot is 256-byte aligned, the slots follow each other in the documented order without gap or overlap,
@@ -13,7 +14,9 @@
 
 #include <vector>
 
-#include "../../celestia-app_amd/csrc/sampling.h"
+#include "../../celestia-app_amd/csrc/befp.h"
+#include "../../celestia-app_amd/csrc/namespace_proof.h"
+#include "../../celestia-app_amd/csrc/share_proof.h"
 
 using namespace cda;
 
@@ -103,7 +106,7 @@ static void check_ns_verify(uint32_t nproofs) {
 }
 
 // Shapes of more than 2^22 slots are measured and compared with the slots' sizes but not bound: nproofs * 2k near
-// 2^41 is no buffer a host can allocate, and the library refuses such calls (check_k in befp.cpp: 2k is bounded by
+// 2^41 is no buffer a host can allocate, and the library refuses such calls (check_axis_shape: 2k is bounded by
 // the axis-root kernel and nproofs * 2k by 2^31).  Every value of the grid is bound on both axes below that.
 static void check_befp(uint32_t k, uint32_t nproofs) {
   BefpArgs a{};

@@ -1,5 +1,5 @@
 // axis_half_rule_dump.cpp — the host form of celestia-app_amd/csrc/axis_half_rule.h and the layout of the
-// workspace its kernels index (axis_half_workspace, csrc/sampling.h), built and run under AddressSanitizer +
+// workspace its kernels index (axis_half_workspace, csrc/axis_half.h), built and run under AddressSanitizer +
 // UndefinedBehaviorSanitizer by tests/test_axis_halves.py, which compares the output line for line with its Python
 // restatement of the rule.  No device is touched (hipcc as the host compiler: the headers need HIP's).
 //   H lines  H0 and what prep and scatter derive, for every descriptor with axis 0..2, index 0..2k, side 0..2 and
@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "../../celestia-app_amd/csrc/axis_half_rule.h"
-#include "../../celestia-app_amd/csrc/sampling.h"
+#include "../../celestia-app_amd/csrc/axis_half.h"
 
 using namespace cda;
 

@@ -1,5 +1,5 @@
-// commitment_arena_check.cpp — CPU check of commit_verify_workspace (celestia-app_amd/csrc/sampling.h), the layout of
-// cda_commitment_proofs_verify's workspace, built and run under AddressSanitizer + UndefinedBehaviorSanitizer by
+// commitment_arena_check.cpp — CPU check of commit_verify_workspace (celestia-app_amd/csrc/commitment.h), the layout
+// of cda_commitment_proofs_verify's workspace, built and run under AddressSanitizer + UndefinedBehaviorSanitizer by
 // tests/test_commitment_proofs.py.  No device is touched.  Like arena_check.cpp: the layout is measured, bound to a
 // heap buffer of exactly the measured size, and every slot is written through the bound pointers over its whole
 // extent, the way the kernels index it (per proof, per row record) -- so a slot the measuring walk did not count is a
@@ -10,7 +10,7 @@
 #include <string.h>
 
 #include "../../celestia-app_amd/csrc/commitment_rule.h"
-#include "../../celestia-app_amd/csrc/sampling.h"
+#include "../../celestia-app_amd/csrc/commitment.h"
 
 using namespace cda;
 

@@ -1,4 +1,4 @@
-// rebuild_arena_check.cpp — CPU check of assemble_workspace (celestia-app_amd/csrc/sampling.h), the layout of
+// rebuild_arena_check.cpp — CPU check of assemble_workspace (celestia-app_amd/csrc/rebuild.h), the layout of
 // cda_samples_assemble_device's workspace, and of the index arithmetic of sample_place_rule.h, built and run under
 // AddressSanitizer + UndefinedBehaviorSanitizer by tests/test_rebuild.py.  No device is touched.  Like arena_check.cpp:
 // the layout is measured, bound to a heap buffer of exactly the measured size, and every slot is written through the
@@ -9,7 +9,7 @@
 #include <string.h>
 
 #include "../../celestia-app_amd/csrc/sample_place_rule.h"
-#include "../../celestia-app_amd/csrc/sampling.h"
+#include "../../celestia-app_amd/csrc/rebuild.h"
 
 using namespace cda;
 

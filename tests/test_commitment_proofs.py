@@ -268,7 +268,7 @@ def test_commitment_kernels_have_no_scratch(kernel, tmp_path):
 
 # ---- workspace layout ----
 def test_verify_workspace_under_asan_ubsan(tmp_path):
-    """commit_verify_workspace (csrc/sampling.h) bound to a heap buffer of exactly its measured size and written
+    """commit_verify_workspace (csrc/commitment.h) bound to a heap buffer of exactly its measured size and written
     through over every slot: tests/san/commitment_arena_check.cpp, a stand-alone host program (hipcc as the host
     compiler: the header needs HIP's; no device code, no device)."""
     exe = str(tmp_path / "commitment_arena_check")

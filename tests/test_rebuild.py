@@ -193,7 +193,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def test_assemble_workspace_and_rule_under_asan_ubsan(tmp_path):
-    """The layout of the assemble workspace (csrc/sampling.h) bound to a heap buffer of exactly its measured size and
+    """The layout of the assemble workspace (csrc/rebuild.h) bound to a heap buffer of exactly its measured size and
     written the way the kernels index it, through csrc/sample_place_rule.h: tests/san/rebuild_arena_check.cpp, a
     stand-alone host program (hipcc as the host compiler: the header needs HIP's; no device code, no device)."""
     exe = str(tmp_path / "rebuild_arena_check")

@@ -1,7 +1,7 @@
 """libcda's host planners (celestia-app_amd/csrc/plan.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer,
 checked against the naive restatements in tests/san/plan_check.cpp (CPU only; scripts/sanitize.sh adds the
 sanitized oracle under the whole CPU suite and keeps the log under profiles/), and the proof calls' carve helper and
-workspace layouts (csrc/arena.h, csrc/sampling.h) under the same sanitizers, bound to exact-size heap buffers by
+workspace layouts (csrc/arena.h, the features' headers) under the same sanitizers, bound to exact-size heap buffers by
 tests/san/arena_check.cpp.  Both are stand-alone programs."""
 import os
 import shutil
@@ -30,9 +30,10 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_proof_workspace_layouts_under_asan_ubsan(tmp_path):
-    """The carve helper (csrc/arena.h) and the three proof workspaces' layouts (csrc/sampling.h) bound to heap buffers
-    of exactly their measured size and written through: tests/san/arena_check.cpp.  The layouts take their structs
-    from a header that needs HIP's, so the host compiler is hipcc's; no device code is built and no device touched."""
+    """The carve helper (csrc/arena.h) and the three proof workspaces' layouts (csrc/share_proof.h, namespace_proof.h,
+    befp.h) bound to heap buffers of exactly their measured size and written through: tests/san/arena_check.cpp.  The
+    layouts take their structs from headers that need HIP's, so the host compiler is hipcc's; no device code is built
+    and no device touched."""
     exe = str(tmp_path / "arena_check")
     subprocess.check_call([HIPCC, "-std=c++17", "-O1", "-g", "--offload-host-only", "-Xarch_host",
                            "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
